@@ -39,8 +39,21 @@ contract (same launch, timing and JSON line; the default is the headline):
   rs173check the same benchmark's other half (ReedSolomonBenchmark.java:73-87,126-149): RS(17,3)
            isParityCorrect over the encoded pool, read-only, one verdict byte per stripe; MB/s of
            data bytes checked (no published figure)
-Every workload's N=1 line carries a cpu_baseline (rank 0, after the timed region): the
+A plain run (``--gpus N --steps K --warmup W``) does what the headline figure needs and no
+more: it builds the resident pool, warms up, times the K steps and prints the line.
+``--full`` adds everything else the line can carry, each in a run of its own around the
+timed region: the byte-compare of the outputs with the erased originals (``verified``),
+the in-run memory ceiling probes (``roofline.measured_ceilings``), the end-to-end leg
+(``e2e``) and, on the N=1 line, the cpu_baseline (rank 0, after the timed region): the
 oracle's restatement of the reference path for that workload on this host's cores.
+--cpu-seconds / --cpu-protocol / --e2e-seconds / --no-verify / --no-probes shape those legs
+under ``--full``; without it the line carries null in their places.
+
+``--dump-outputs DIR`` writes what the last timed step computed (Workload.outputs(): the
+arrays a caller of the timed launch receives) as DIR/<name>.npy in float32, after the timed
+region.  Outputs above DUMP_ELEMS elements are sampled in DUMP_BLOCK-byte blocks at fixed,
+seeded positions (sample_output), the same in every run; the pool is seeded too, so two
+builds of the library can be compared output for output.
 """
 import argparse
 import json
@@ -108,16 +121,22 @@ def parse():
     ap.add_argument("--pitch-pad", type=int, default=0,
                     help="rs124: bytes of padding per 4 MiB shard (default 0: the natural contiguous [S][16][4 MiB] layout)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="CPU baseline on: > 0 (the bounded protocol's all-thread sample length); 0 = skip")
+                    help="--full: CPU baseline on: > 0 (the bounded protocol's all-thread sample length); 0 = skip")
     ap.add_argument("--cpu-protocol", default="reference", choices=["bounded", "reference"],
                     help="reference (default): BASELINE.md section 4 / ReedSolomonBenchmark.java:104-124, 2 warm-ups + "
                          "the mean of 10 x 2 s measurements per thread count (~50 s on rank 0 after the timed region); "
                          "bounded: one sample of cpu-seconds/2 on one thread and one of cpu-seconds on all")
     ap.add_argument("--e2e-seconds", type=float, default=2.0,
-                    help="end-to-end leg (pinned host -> H2D -> kernel -> D2H) after the timed region, on every "
+                    help="--full: end-to-end leg (pinned host -> H2D -> kernel -> D2H) after the timed region, on every "
                          "rank at once: > 0 = its length in seconds; 0 = skip")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-probes", action="store_true", help="skip the in-run memory ceiling probes")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: output verification, memory ceiling "
+                         "probes, the end-to-end leg and the CPU baseline (off: their fields are null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32; a "
+                         "fixed, seeded sample of outputs above %d elements)" % DUMP_ELEMS)
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the output verification")
+    ap.add_argument("--no-probes", action="store_true", help="--full: skip the in-run memory ceiling probes")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="launch-shape knob (include/ecx_tune.h), for A/B runs; repeatable")
     ap.add_argument("--meta", default=None, help="write the launch metadata (kernel, pool, bytes per launch, "
@@ -533,6 +552,38 @@ def memory_probes(ecx, torch, region, reads: int, writes: int, reps: int = 5):
             "mix_model_GBps": round(mix, 1)}
 
 
+DUMP_ELEMS = 8 << 20   # elements --dump-outputs writes per run, over all arrays: 32 MiB of float32
+DUMP_BLOCK = 4096      # bytes per sampled block of an output too large to write whole
+DUMP_SEED = 0xD0C5     # of the sampled block positions: the same in every run
+
+
+def sample_output(torch, t, budget: int):
+    """The uint8 tensor `t` as a flat float32 host array of at most `budget` elements: all of
+    it if it fits, else its first and last DUMP_BLOCK-byte blocks and a seeded choice of the
+    others, in ascending order (the positions depend on t's size and the budget only)."""
+    import numpy as np
+    flat = t.reshape(-1)
+    if flat.numel() > budget:
+        nblk = flat.numel() // DUMP_BLOCK
+        take = max(2, budget // DUMP_BLOCK)
+        rng = np.random.default_rng(DUMP_SEED)
+        ids = np.unique(np.concatenate(([0, nblk - 1], 1 + rng.choice(nblk - 2, take - 2, replace=False))))
+        flat = flat[:nblk * DUMP_BLOCK].view(nblk, DUMP_BLOCK)[torch.from_numpy(ids).to(flat.device)].reshape(-1)
+    return flat.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(torch, wl, directory, rank: int = 0):
+    """Write wl.outputs() as <directory>/<name>.npy (rank 0; the other ranks of a multi-GPU run
+    add _rank<r> to the name), DUMP_ELEMS elements in all, shared equally among the arrays."""
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    outs = wl.outputs()
+    for name, t in outs.items():
+        arr = sample_output(torch, t, DUMP_ELEMS // len(outs))
+        np.save(d / ("%s%s.npy" % (name, "_rank%d" % rank if rank else "")), arr)
+
+
 class Workload:
     """A resident pool of valid stripes and one batch launch over all of it."""
     unit_bytes = ALGO_BYTES           # algorithmic bytes per stripe (BASELINE.md section 3)
@@ -554,6 +605,10 @@ class Workload:
 
     def verify(self) -> bool:
         raise NotImplementedError
+
+    def outputs(self) -> dict:
+        """name -> device tensor (uint8): what a caller of launch() receives (--dump-outputs)."""
+        return {"repaired": self.out}
 
     def sample(self):
         """(one pool unit, the GPU's output for it) as host arrays, for oracle_check."""
@@ -927,6 +982,9 @@ class RS124(_RsLayout, Workload):
         return all(bool(self.torch.equal(self.stripes(s0, min(64, self.P - s0), [0, 1]), self.orig[s0:s0 + 64]))
                    for s0 in range(0, self.P, 64))
 
+    def outputs(self):
+        return {"decoded": self.stripes(0, self.P, [0, 1])}
+
     def sample(self):
         s = self.P // 2
         st = self.stripes(s, 1)[0]
@@ -1015,6 +1073,9 @@ class RS173(_RsLayout, Workload):
         same = bool(self.torch.equal(before, self.pool))
         del before
         return same and all(self.oracle_check(*self._stripe_and_parity(s)) for s in (0, self.P - 1))
+
+    def outputs(self):
+        return {"parity": self.stripes(0, self.P, list(range(self.k, self.n)))}
 
     def _stripe_and_parity(self, s):
         st = self.stripes(s, 1)[0]
@@ -1106,6 +1167,9 @@ class RS173Check(RS173):
         self.torch.cuda.synchronize()
         return ok and bool((self.verdict == 1).all())
 
+    def outputs(self):
+        return {"verdict": self.verdict}
+
     def sample(self):
         s_ = self.P // 2
         return self.pool[s_].cpu().numpy(), self.verdict[s_:s_ + 1].cpu().numpy()
@@ -1182,6 +1246,9 @@ class LRCEncode(Workload):
         same = bool(self.torch.equal(before, self.pool[:, 3::4]))
         return same and all(self.oracle_check(self.pool[s].cpu().numpy(), self.pool[s, 3::4].cpu().numpy())
                             for s in (0, self.P - 1))
+
+    def outputs(self):
+        return {"parity": self.pool[:, 3::4]}
 
     def host_units(self, k):
         # CPU units are local groups (3 data blocks + parity), as the reference encodes them
@@ -1369,7 +1436,8 @@ def main():
     kernel = ecx.last_kernel()  # the instance launch_apply actually chose for this map and layout
     rss_stages["pool"] = _peak_rss_bytes()
     verified = None
-    if not args.no_verify:
+    verify = args.full and not args.no_verify
+    if verify:
         verified = wl.verify()
         if not verified:
             raise SystemExit("repair output differs from the erased originals")
@@ -1393,7 +1461,7 @@ def main():
         state, dropped = gm.layout_state(pitch)
         launch_shape = {"layout_select": choice, "candidate_median_ms": med, "kernel": kernel,
                         "state": state, "probes_dropped": dropped}
-        if not args.no_verify and not wl.verify():
+        if verify and not wl.verify():
             raise SystemExit("output differs from the erased originals after the layout selection")
 
     for _ in range(args.warmup):
@@ -1429,6 +1497,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
 
+    if args.dump_outputs:
+        dump_outputs(torch, wl, args.dump_outputs, rank)
+
     launch_times = [a.elapsed_time(b) for a, b in evs]
     launch_ms = sum(launch_times) / len(launch_times)
     # the spread of the timed launches, first and last step apart: a memory system still busy
@@ -1455,7 +1526,7 @@ def main():
     # the end-to-end leg: every rank at once (they share the host's PCIe and memory), after the
     # timed region; the line carries rank 0's figures and the whole-job sum
     e2e = None
-    if args.e2e_seconds > 0:
+    if args.full and args.e2e_seconds > 0:
         if grouped:
             dist.barrier()
         rss_before = _peak_rss_bytes()  # the process before the leg: torch + HIP runtime, the bench's own state
@@ -1480,10 +1551,10 @@ def main():
                            per_rank_GiBps=[round(r, 3) for r in rates], peak_rss=rss)
 
     sample = units = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:  # the contract: rank 0 at N=1 only
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:  # the contract: rank 0 at N=1 only
         sample = wl.sample()  # one pool unit for the oracle check
         units = wl.host_units(8 if wl.unit_bytes < (64 << 20) else (2 if wl.unit_bytes < (1 << 30) else 1))
-    probes = memory_probes(ecx, torch, wl.region, wl.reads, wl.writes) if not args.no_probes else None
+    probes = memory_probes(ecx, torch, wl.region, wl.reads, wl.writes) if args.full and not args.no_probes else None
 
     cpu = None
     if sample is not None:  # rank 0 at N=1 only, after the timed region
@@ -1508,6 +1579,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(el / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "weak",

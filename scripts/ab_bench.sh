@@ -15,7 +15,7 @@ for ((r = 0; r < ROUNDS; r++)); do
     IFS=',' read -r -a kv <<< "${S[$i]}"
     for t in "${kv[@]}"; do [ -n "$t" ] && args+=(--tune "$t"); done
     log="$OUT/ab_${WL}_${r}_$i.log"
-    timeout -k 10 300 python bench.py --workload "$WL" --steps 3 --warmup 1 --cpu-seconds 0 --no-probes \
+    timeout -k 10 300 python bench.py --full --workload "$WL" --steps 3 --warmup 1 --cpu-seconds 0 --no-probes \
         "${args[@]}" > "$log" 2>&1
     rc=$?; [ $rc -ne 0 ] && { echo "rc=$rc"; tail -5 "$log"; exit $rc; }
     python - "$log" "$WL" "${S[$i]}" <<'PY' | tee -a "$OUT/ab_bench.jsonl"

@@ -7,7 +7,7 @@ WL="${WL:-clay104}"
 EXTRA="${EXTRA:-}"
 for W in $WL; do
   for V in ${VALS:-0 1 1 0}; do
-    timeout -k 10 300 python bench.py --workload $W --steps 3 --warmup 1 --cpu-seconds 0 --no-probes \
+    timeout -k 10 300 python bench.py --full --workload $W --steps 3 --warmup 1 --cpu-seconds 0 --no-probes \
         --tune ${KNOB:-bitslice}=$V $EXTRA > "$OUT/ab_${W}_$V.log" 2>&1
     rc=$?; [ $rc -ne 0 ] && { echo "rc=$rc"; tail -5 "$OUT/ab_${W}_$V.log"; exit $rc; }
     python - "$OUT/ab_${W}_$V.log" "$W" "$V" "${KNOB:-bitslice}" <<'PY' | tee -a "$OUT/ab_knob.jsonl"

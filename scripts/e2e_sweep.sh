@@ -9,7 +9,7 @@ W=${1:-clay42}
 for CH in 16384 65536 262144; do
   for NB in 2 3 4; do
     L="$OUT/e2e_${W}_${CH}_${NB}.log"
-    timeout -k 10 200 python bench.py --workload $W --steps 1 --warmup 0 --cpu-seconds 0 --no-probes --e2e-seconds 3 \
+    timeout -k 10 200 python bench.py --full --workload $W --steps 1 --warmup 0 --cpu-seconds 0 --no-probes --e2e-seconds 3 \
         --tune host_chunk_kib=$CH --tune host_buffers=$NB > "$L" 2>&1
     rc=$?; [ $rc -ne 0 ] && { echo "bench $W $CH $NB rc=$rc"; tail -3 "$L"; exit $rc; }
     python -c "

@@ -33,30 +33,30 @@ if has pmc; then
       || stop pmc_summary $?
 fi
 if has bench; then
-  timeout -k 10 600 python bench.py --steps 5 --warmup 2 > "$OUT/bench.log" 2>&1
+  timeout -k 10 600 python bench.py --full --steps 5 --warmup 2 > "$OUT/bench.log" 2>&1
   rc=$?; echo "bench rc=$rc"; tail -2 "$OUT/bench.log"; [ $rc -ne 0 ] && stop bench $rc
 fi
 if has gloo2; then
   # the multi-rank path without an external launcher, 2 ranks sharing the one GPU
-  ECX_BENCH_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 2 --pool 4096 --steps 2 --warmup 1 \
+  ECX_BENCH_BACKEND=gloo timeout -k 10 600 python bench.py --full --gpus 2 --pool 4096 --steps 2 --warmup 1 \
       --cpu-seconds 4 --no-probes > "$OUT/bench_gloo2.log" 2>&1
   rc=$?; echo "bench gloo2 rc=$rc"; tail -2 "$OUT/bench_gloo2.log"; [ $rc -ne 0 ] && stop gloo2 $rc
 fi
 if has workloads; then
   for W in clay104 rs124 lrc clay42x2 rs173 lrcenc rs173check; do
-    timeout -k 10 300 python bench.py --workload $W --steps 3 --warmup 1 > "$OUT/bench_$W.log" 2>&1
+    timeout -k 10 300 python bench.py --full --workload $W --steps 3 --warmup 1 > "$OUT/bench_$W.log" 2>&1
     rc=$?; echo "bench $W rc=$rc"; tail -1 "$OUT/bench_$W.log"; [ $rc -ne 0 ] && stop "bench $W" $rc
   done
 fi
 if has refcpu; then
   # the headline line with BASELINE.md section 4's CPU protocol (2 warm-ups + 10 x 2 s)
-  timeout -k 10 600 python bench.py --steps 5 --warmup 2 --cpu-protocol reference > "$OUT/bench_refcpu.log" 2>&1
+  timeout -k 10 600 python bench.py --full --steps 5 --warmup 2 --cpu-protocol reference > "$OUT/bench_refcpu.log" 2>&1
   rc=$?; echo "bench refcpu rc=$rc"; tail -1 "$OUT/bench_refcpu.log"; [ $rc -ne 0 ] && stop "bench refcpu" $rc
 fi
 if has prof; then
   export TMPDIR=/tmp
   (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run \
-      -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --cpu-seconds 0 --e2e-seconds 0) > "$OUT/prof.log" 2>&1
+      -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --cpu-seconds 0 --e2e-seconds 0) > "$OUT/prof.log" 2>&1
   rc=$?; echo "rocprof rc=$rc"; tail -2 "$OUT/prof.log"; [ $rc -ne 0 ] && stop prof $rc
   find "$OUT/prof" -name '*stats*'
 fi

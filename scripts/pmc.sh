@@ -63,7 +63,7 @@ for W in $WORKLOADS; do
     for C in "${PASSES[@]}"; do
       D="$OUT/pmc_${W}${TAG}_$i"; mkdir -p "$D"
       timeout -s KILL 240 rocprofv3 --pmc $C --output-format csv -d "$D" -o run \
-          -- python3 "$ROOT/bench.py" $(variant_args "$W") --steps 1 --warmup 0 --cpu-seconds 0 --e2e-seconds 0 \
+          -- python3 "$ROOT/bench.py" --full $(variant_args "$W") --steps 1 --warmup 0 --cpu-seconds 0 --e2e-seconds 0 \
              --stripes-per-step $((POOL * 16)) --no-probes --meta "$D/meta.json" "${TUNE[@]}" > "$D.log" 2>&1
       rc=$?; echo "pmc $W$TAG pass$i rc=$rc"; [ $rc -ne 0 ] && { tail -5 "$D.log"; exit $rc; }
       i=$((i + 1))

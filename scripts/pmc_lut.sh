@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 cd /tmp
 VARIANTS=("lds_lut=0" "lds_lut=1" "lds_lut=2")
 for V in "${VARIANTS[@]}"; do
-  timeout -k 10 300 python3 "$ROOT/bench.py" --steps 3 --warmup 1 --cpu-seconds 0 --tune "$V" \
+  timeout -k 10 300 python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --cpu-seconds 0 --tune "$V" \
       > "$OUT/lut_bench_$V.log" 2>&1
   rc=$?; echo "bench $V rc=$rc"; [ $rc -ne 0 ] && exit $rc
   tail -1 "$OUT/lut_bench_$V.log" >> "$OUT/lut_bench.jsonl"

@@ -18,7 +18,7 @@ for TAG in A B; do
   for S in "${SETS[@]}"; do
     D="$OUT/sqab_${WL}_${TAG}_$i"; mkdir -p "$D"
     timeout -s KILL 240 rocprofv3 --pmc $S --output-format csv -d "$D" -o run \
-        -- python3 "$ROOT/bench.py" --workload "$WL" --steps 1 --warmup 0 --cpu-seconds 0 \
+        -- python3 "$ROOT/bench.py" --full --workload "$WL" --steps 1 --warmup 0 --cpu-seconds 0 \
            --stripes-per-step "$POOL" --no-probes --tune "$TUNE" --meta "$D/meta.json" > "$D.log" 2>&1
     rc=$?; echo "sq $WL $TAG set$i rc=$rc"; [ $rc -ne 0 ] && { tail -5 "$D.log"; exit $rc; }
     i=$((i + 1))

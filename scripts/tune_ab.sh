@@ -14,7 +14,7 @@ for W in ${*:-clay42 rs173 lrcenc}; do
   i=0
   for V in $A $B $B $A $A $B; do
     L="$OUT/tune_ab_${KEY}_${W}_${i}.log"
-    timeout -k 10 200 python bench.py --workload $W --steps 5 --warmup 2 --no-probes --cpu-seconds 0 --e2e-seconds 0 \
+    timeout -k 10 200 python bench.py --full --workload $W --steps 5 --warmup 2 --no-probes --cpu-seconds 0 --e2e-seconds 0 \
         --tune "$KEY=$V" "${EXTRA[@]}" > "$L" 2>&1
     rc=$?; [ $rc -ne 0 ] && { echo "bench $W $KEY=$V rc=$rc"; tail -3 "$L"; exit $rc; }
     python -c "

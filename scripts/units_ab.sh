@@ -8,7 +8,7 @@ ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$ROOT/gpurun_out"; mkdir -p "$OUT"; cd "$ROOT"
 for W in ${*:-clay42 rs173 rs124 lrcenc lrc}; do
   for U in 1 2 4 4 2 1; do
-    timeout -k 10 200 python bench.py --workload $W --steps 5 --warmup 2 --no-probes --cpu-seconds 0 --e2e-seconds 0 \
+    timeout -k 10 200 python bench.py --full --workload $W --steps 5 --warmup 2 --no-probes --cpu-seconds 0 --e2e-seconds 0 \
         --tune units=$U --tune layout_select=0 > "$OUT/units_ab_${W}_$U.log" 2>&1
     rc=$?; [ $rc -ne 0 ] && { echo "bench $W units=$U rc=$rc"; tail -3 "$OUT/units_ab_${W}_$U.log"; exit $rc; }
     python -c "

@@ -291,6 +291,57 @@ def test_e2e_leg_fills_in_chunks_within_the_budget(monkeypatch):
     assert "skipped" in r and r["host_cap"]["world"] == 8
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """A plain run leaves every leg beside the timed steps off; --full and --dump-outputs opt in."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: an output within the budget is written whole; a larger one as its first
+    and last blocks plus a seeded choice of the others, the same positions in every run, so two
+    runs on the same data give the same file and a changed byte in a sampled block shows."""
+    import numpy as np
+    import torch
+    small = torch.arange(1000, dtype=torch.int64).to(torch.uint8)
+    assert np.array_equal(bench.sample_output(torch, small, 1000), small.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BLOCK", 16)
+    big = torch.randint(0, 256, (50, 8, 40), dtype=torch.uint8)  # 1000 blocks of 16 B
+    flat = big.reshape(-1).numpy()
+    got = bench.sample_output(torch, big, 160)
+    assert got.dtype == np.float32 and got.size == 160
+    assert np.array_equal(got[:16], flat[:16]) and np.array_equal(got[-16:], flat[-16:])
+    assert np.array_equal(got, bench.sample_output(torch, big.clone(), 160))
+    # every sampled block is a block of the output, in ascending order
+    blocks = {flat[i:i + 16].tobytes(): i for i in range(0, flat.size, 16)}
+    at = [blocks[got[i:i + 16].astype(np.uint8).tobytes()] for i in range(0, 160, 16)]
+    assert at == sorted(at) and len(set(at)) == 10
+    changed = big.clone()
+    changed.view(-1)[at[3] + 5] ^= 1
+    assert not np.array_equal(got, bench.sample_output(torch, changed, 160))
+    # the files: one per output, DUMP_ELEMS in all, rank 0 under the plain name
+    monkeypatch.setattr(bench, "DUMP_ELEMS", 320)
+    wl = _bare(bench.RS173Check, verdict=torch.ones(7, dtype=torch.uint8))
+    bench.dump_outputs(torch, wl, tmp_path / "a")
+    assert np.array_equal(np.load(tmp_path / "a" / "verdict.npy"), np.ones(7, np.float32))
+    wl = _bare(bench.Clay42, out=big)
+    bench.dump_outputs(torch, wl, tmp_path / "a")
+    bench.dump_outputs(torch, wl, tmp_path / "b", rank=1)
+    a, b = np.load(tmp_path / "a" / "repaired.npy"), np.load(tmp_path / "b" / "repaired_rank1.npy")
+    assert a.dtype == np.float32 and a.size == 320 and np.array_equal(a, b)
+    # the in-place workloads hand out the slots the launch wrote
+    pool = torch.randint(0, 256, (3, 16, 8), dtype=torch.uint8)
+    assert torch.equal(_bare(bench.LRCEncode, pool=pool).outputs()["parity"], pool[:, [3, 7, 11, 15]])
+    rs = _bare(bench.RS173, pool=torch.randint(0, 256, (3, 20, 12), dtype=torch.uint8), P=3, L=10)
+    assert torch.equal(rs.outputs()["parity"], rs.pool[:, 17:, :10])
+    r12 = _bare(bench.RS124, pool=torch.randint(0, 256, (3, 16, 12), dtype=torch.uint8), P=3, L=10)
+    assert torch.equal(r12.outputs()["decoded"], r12.pool[:, :2, :10])
+
+
 def test_copy_chunked_round_trip():
     import torch
     src = torch.randint(0, 256, (12345,), dtype=torch.uint8)
