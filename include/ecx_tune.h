@@ -239,6 +239,16 @@ int ecx_last_kernel(char *buf, int len);
  * encode -- "k_gf_apply<...> stagger=G xcd_group=X xcd_run=R [skew=K]" for the composed-map
  * kernels, the bare name for the generated Clay kernels.  Same buffer contract. */
 int ecx_last_launch_shape(char *buf, int len);
+/* What ecx_last_launch_shape would report after ecx_map_apply_batch (accumulate != 0:
+ * ecx_map_accumulate_batch) of this batch layout under the current knobs, decided by the same
+ * launch rules (csrc/launch_rules.hpp) but host-only: no device is touched and nothing is
+ * launched.  in_addr / out_addr are the buffers' addresses as integers (only their alignment and
+ * overlap matter); cand is the "layout_select" candidate to plan for, 0 = the static rules.
+ * A generated kernel the rules would pick is taken to compile.  Same buffer contract; length 0 =
+ * a call that launches no full-chunk kernel and leaves the last shape as it was. */
+int ecx_map_launch_plan(const struct ecx_map *map, uint64_t in_addr, int64_t in_stripe_stride, int64_t in_slot_stride,
+                        uint64_t out_addr, int64_t out_stripe_stride, int64_t out_slot_stride, int64_t nstripes,
+                        int64_t byte_count, int accumulate, int cand, char *buf, int len);
 /* The per-helper-plane Clay repair kernel (ecx_tune "clay_rtc"): builds the clay
  * step's repair program (checked against the composed reference map), generates the
  * kernel source and compiles it with hiprtc for gfx950 -- no device needed.  Returns

@@ -531,6 +531,22 @@ class GfMap:
                 "slices")
         return {k: int(v) for k, v in zip(keys, out)}
 
+    def launch_plan(self, in_addr, in_stripe_stride, in_slot_stride, out_addr, out_stripe_stride, out_slot_stride,
+                    nstripes, byte_count, accumulate: bool = False, cand: int = 0) -> str:
+        """What last_launch_shape() would report after apply_batch (accumulate_batch) of this layout
+        under the current knobs (ecx_map_launch_plan, host-only: nothing is launched).  The buffers
+        are given as integer addresses; cand is the "layout_select" candidate, 0 = the static
+        rules.  "" for a call that launches no full-chunk kernel."""
+        f = lib().ecx_map_launch_plan
+        I64, U64 = ctypes.c_int64, ctypes.c_uint64
+        f.argtypes = [ctypes.c_void_p, U64, I64, I64, U64, I64, I64, I64, I64, ctypes.c_int, ctypes.c_int,
+                      ctypes.c_char_p, ctypes.c_int]
+        f.restype = ctypes.c_int
+        buf = ctypes.create_string_buffer(512)
+        n = check(f(self._h, int(in_addr), in_stripe_stride, in_slot_stride, int(out_addr), out_stripe_stride,
+                    out_slot_stride, nstripes, byte_count, int(bool(accumulate)), int(cand), buf, len(buf)))
+        return buf.value.decode() if n > 0 else ""
+
     def layout_state(self, slot_pitch: int):
         """(state, dropped probes) of that layout's selection (ecx_map_layout_state): state -1
         none yet, 0 exploring, 1 chosen, 2 re-validating, 3 re-validated, 4 contended."""

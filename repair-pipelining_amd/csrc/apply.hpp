@@ -383,6 +383,7 @@ struct Shape {
     int threads;
     int rows;  // kTileRows, or 2 / 4 for maps whose tiles all have at most that many rows
     bool tail = false;  // k_gf_apply_tail: ApplyArgs::tail_chunk is in the launch
+    bool note = true;   // the launch names the call (Launch::of_record; byte-safe launches never do)
 };
 
 template <int T>
@@ -406,6 +407,5 @@ void launch_bits(bool ntl, int depth, dim3 grid, hipStream_t stream, const Apply
 // product rows (single-tile maps, `pairs` general coefficients) -- over n_units
 // (stripe, 4 KiB chunk, tile) units of the depth-4 padded plan, persistent workgroups.
 void launch_lut(int mode, bool ntl, int pairs, int64_t n_units, hipStream_t stream, const ApplyArgs &a);
-constexpr int kLutMaxPairs = 256;  // mode 1: 64 KiB of product rows per workgroup at most
 
 }  // namespace ecx

@@ -117,7 +117,7 @@ void launch_check_core(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_str
     a.n_tiles = cm.n_tiles();
     a.stagger = tu.stagger;
     // inputs not 128-B aligned share a boundary line between neighbouring chunks: runs of
-    // consecutive units per XCD keep both fetches in one L2 (as launch_apply_core does)
+    // consecutive units per XCD keep both fetches in one L2 (as launch_rules.cpp choose_launch does)
     const bool misaligned128 = ((uintptr_t)in % 128) != 0 || in_stripe_stride % 128 != 0 || in_slot_stride % 128 != 0;
     a.xcd_group = tu.xcd_group == 3 ? 3 : (tu.xcd_misaligned && misaligned128 ? 3 : 0);
     a.xcd_run = tu.xcd_run;

@@ -13,35 +13,44 @@ void launch_k(dim3 grid, size_t lds, hipStream_t stream, const ApplyArgs &a) {
 // 20 / 24; 20 also with scoped stores) for single tiles with NT loads, SGPR tables and
 // 256-thread workgroups; the small-tile variants (2 or 4 rows, NT loads and stores,
 // depth 4 / 8 / 12) for 256-thread workgroups.
-// launch_apply only asks for shapes that exist (it clamps the others).  `lds` is the TLDS
+// The launch rules (launch_rules.cpp choose_launch) only ask for shapes that exist: they do all
+// the clamping, and a shape without an instance is refused here.  `lds` is the TLDS
 // table bytes plus ecx_tune "occ_lds" (0 by default) for every non-byte-safe instance.
 template <int T>
 void launch_shape_t(const Shape &s, dim3 grid, size_t lds, hipStream_t stream, const ApplyArgs &a) {
-    if (s.tail) {  // launch_apply_core asks for it only on this shape
+    const auto no_instance = [] { return Error(ECX_E_ILLEGAL_ARGUMENT, "no k_gf_apply instance for this launch shape"); };
+    if (s.tail) {  // the rules ask for it only on this shape
         if (s.safe || !s.ntl || s.nts != 1 || s.tlds || s.rows != kTileRows || (s.depth != 4 && s.depth != 8))
             throw Error(ECX_E_ILLEGAL_ARGUMENT, "no k_gf_apply_tail instance for this launch shape");
-        note_kernel("k_gf_apply_tail", true, 1, s.depth, false, T, kTileRows);
+        if (s.note) note_kernel("k_gf_apply_tail", true, 1, s.depth, false, T, kTileRows);
         if (s.depth == 8) hipLaunchKernelGGL((k_gf_apply_tail<true, 1, 8, false, T, kTileRows>), grid, dim3(T), 0, stream, a);
         else hipLaunchKernelGGL((k_gf_apply_tail<true, 1, 4, false, T, kTileRows>), grid, dim3(T), 0, stream, a);
         return;
     }
     if (s.safe) {  // the byte-safe kernel's ring must match the plan's padding
-        if (s.depth % 4) return launch_k<true, false, 0, 2, false, T>(grid, 0, stream, a);
-        return launch_k<true, false, 0, 4, false, T>(grid, 0, stream, a);
+        if (s.depth == 2) return launch_k<true, false, 0, 2, false, T>(grid, 0, stream, a);
+        if (s.depth == 4) return launch_k<true, false, 0, 4, false, T>(grid, 0, stream, a);
+        throw no_instance();
     }
+    if (s.ntl ? s.nts == 0 : s.nts < 0 || s.nts > 2) throw no_instance();
+    if (T != kBlockThreads && s.nts != 1) throw no_instance();  // one-wave workgroups: plain-nt stores only
     if constexpr (T == kBlockThreads) {
         if (s.rows < kTileRows) {
+            if (!s.ntl || s.nts != 1 || s.tlds) throw no_instance();
             auto small = [&](auto rows) {
                 constexpr int R = decltype(rows)::value;
                 if (s.depth == 12) launch_k<false, true, 1, 12, false, T, R>(grid, lds, stream, a);
                 else if (s.depth == 8) launch_k<false, true, 1, 8, false, T, R>(grid, lds, stream, a);
-                else launch_k<false, true, 1, 4, false, T, R>(grid, lds, stream, a);
+                else if (s.depth == 4) launch_k<false, true, 1, 4, false, T, R>(grid, lds, stream, a);
+                else throw no_instance();
             };
             if (s.rows == 2) small(std::integral_constant<int, 2>{});
-            else small(std::integral_constant<int, 4>{});
+            else if (s.rows == 4) small(std::integral_constant<int, 4>{});
+            else throw no_instance();
             return;
         }
     }
+    if (s.rows != kTileRows) throw no_instance();
     auto by_depth = [&](auto ntl, auto nts) {
         constexpr bool L = decltype(ntl)::value;
         constexpr int S = decltype(nts)::value;
@@ -75,6 +84,7 @@ void launch_shape_t(const Shape &s, dim3 grid, size_t lds, hipStream_t stream, c
                 return;
             }
         }
+        if (s.depth != 4) throw no_instance();
         if (s.tlds) launch_k<false, L, S, 4, true, T>(grid, lds, stream, a);
         else launch_k<false, L, S, 4, false, T>(grid, lds, stream, a);
     };

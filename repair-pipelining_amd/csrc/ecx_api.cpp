@@ -1691,6 +1691,24 @@ int ecx_map_host_plan(const ecx_map *map, int64_t in_stripe_stride, int64_t in_s
     });
 }
 
+int ecx_map_launch_plan(const ecx_map *map, uint64_t in_addr, int64_t in_stripe_stride, int64_t in_slot_stride,
+                        uint64_t out_addr, int64_t out_stripe_stride, int64_t out_slot_stride, int64_t nstripes,
+                        int64_t byte_count, int accumulate, int cand, char *buf, int len) {
+    return guarded(__func__, [&]() -> int {
+        if (!map) throw Error(ECX_E_NULL, "null map");
+        const int pick = layout_candidate_code(cand);
+        if (pick == -2) throw Error(ECX_E_ILLEGAL_ARGUMENT, "no such layout candidate");
+        const BatchLayout b{(uintptr_t)in_addr, (uintptr_t)out_addr, in_stripe_stride, in_slot_stride, out_stripe_stride,
+                            out_slot_stride,    nstripes,            byte_count,       accumulate != 0};
+        // no device here: a generated bit-plane kernel the auto rule asks for is taken to build
+        const std::string s = describe(choose_launch(map->cm.traits(), tuning(), b, pick, ECX_DIAG != 0,
+                                                     {[](void *) { return true; }, nullptr}));
+        if (!buf || len < (int)s.size() + 1) return ECX_E_ILLEGAL_ARGUMENT;
+        std::memcpy(buf, s.c_str(), s.size() + 1);
+        return (int)s.size();
+    });
+}
+
 int ecx_last_launch_shape(char *buf, int len) {
     const std::string k = last_launch_shape();
     if (!buf || len < (int)k.size() + 1) return ECX_E_ILLEGAL_ARGUMENT;

@@ -362,6 +362,33 @@ CompiledMap::CompiledMap(LinearMap m) : map_(std::move(m)) {
     // runs, scripts/depth_bench.py, profiles/r01_depth.jsonl).  Shorter or narrower
     // tiles (RS decode, LRC) measured flat or slower with deep rings.
     if (n_tiles_ == 1 && max_tile_rows_ == kTileRows && min_count > 16 && min_count <= 20) preferred_depth_ = 20;
+
+    MapTraits &t = traits_;
+    t.n_tiles = n_tiles_;
+    t.n_groups = n_groups_;
+    t.group_size = group_size_;
+    t.n_wide_tiles = n_wide_;
+    t.wide_sharing = wide_sharing();
+    t.wide_depth = wide_depth_;
+    t.preferred_depth = preferred_depth_;
+    t.max_tile_rows = max_tile_rows_;
+    t.max_in_slot = max_in_slot_;
+    t.max_out_slot = max_out_slot_;
+    t.n_in = map_.n_in;
+    t.n_out = map_.n_out;
+    t.nnz = map_.nnz();
+    for (int j = 0; j < map_.n_in; ++j) {
+        bool used = false;
+        for (int o = 0; o < map_.n_out; ++o) {
+            used |= map_.at(o, j) != 0;
+            t.general_coeffs += map_.at(o, j) > 1;
+        }
+        t.used_inputs += used;
+    }
+    t.planes_supported = map_planes_supported(map_);
+    for (int i = 0; i < n_tiles_; ++i) t.max_tile_count = std::max(t.max_tile_count, (int)tiles_[(size_t)i * kTileDwords + 1]);
+    for (int o : map_.out_slot)
+        for (int i : map_.in_slot) t.slots_intersect |= o == i;
 }
 
 void CompiledMap::emulate(const uint8_t *in, uint8_t *out, int64_t len, bool via_unions) const {

@@ -18,7 +18,7 @@ sys.path.insert(0, str(ROOT))
 import rpamd  # noqa: E402
 
 TOTAL = 16 << 30
-# launch_apply_core's pick codes (kernels.hip kLayoutCand) as tune knobs
+# choose_launch's pick codes (launch_rules.hpp kLayoutCand) as tune knobs
 FORCED = {-1: {"layout_select": 0}, 0: {"skew_chunks": 0, "block_threads": 256}, 1: {"skew_chunks": 4},
           2: {"skew_chunks": 0, "block_threads": 64}, 18: {"skew_chunks": 0, "block_threads": 64, "stagger": 2},
           66: {"skew_chunks": 0, "block_threads": 64, "stagger": 8},

@@ -1449,7 +1449,7 @@ def test_partial_last_chunk_in_main_launch(ecx, torch_dev, nbytes):
     """A shard whose byte count is a multiple of 16 but not of the chunk (RS(17,3) on the
     published 200,000-B shards) runs its partial last chunk in the main k_gf_apply launch
     as a workgroup over the shard's last chunk-sized window that stores only the partial
-    chunk (kernels.hip launch_apply_core); shards shorter than one chunk and layouts whose
+    chunk (launch_rules.cpp choose_launch); shards shorter than one chunk and layouts whose
     outputs are inputs of the same launch keep the byte-safe launch.  RS(17,3) encode in place
     (3 rows), a 2-row decode to a separate buffer in 256-thread and one-wave workgroups,
     overwrite and accumulate, and an in-place map whose output slot is also an input slot:
@@ -2882,3 +2882,120 @@ def test_host_check_batch_random_layouts(ecx):
             assert verdict.tolist() == want, (case, k, m, L, off, win, pitch, S)
     finally:
         ecx.tune("host_chunk_kib", 65536)
+
+
+def _recorder():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("record_launch_shapes",
+                                                  Path(__file__).resolve().parents[1] / "scripts" / "record_launch_shapes.py")
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    return rec
+
+
+def _plans_name_what_runs(ecx, torch, cases, want):
+    """For each (map, nbytes, pitch kind, stripes, in place, accumulate, knobs) case: what
+    GfMap.launch_plan says before the launch is what ecx.last_launch_shape() says after it, the
+    output equals the default shape's, and the cases reach every kernel family of `want`."""
+    rec = _recorder()
+    maps = rec.build_maps(ecx)
+
+    def knobs(k):
+        rec.set_knob(ecx, "")
+        for kv in filter(None, k.split(",")):
+            key, _, v = kv.partition("=")
+            ecx.tune(key, int(v))
+
+    srcs, refs, families = {}, {}, set()
+
+    def run(name, n, p, S, ip, acc):
+        gmap = maps[name]
+        case = {"n": n, "p": p, "o": 0, "ip": ip, "S": S}
+        io, iss, isl, oo, oss, osl, in_bytes, out_bytes = rec.layout(gmap, case)
+        if (name, n, p, S) not in srcs:
+            src = torch.empty(in_bytes, dtype=torch.uint8, device="cuda")
+            ecx.fill_random(src, src.numel(), 77 + n)
+            srcs[(name, n, p, S)] = src
+        inp = srcs[(name, n, p, S)].clone()
+        out = inp if ip else torch.full((out_bytes,), 0x5A, dtype=torch.uint8, device="cuda")
+        plan = gmap.launch_plan(inp.data_ptr(), iss, isl, out.data_ptr(), oss, osl, S, n, bool(acc))
+        (gmap.accumulate_batch if acc else gmap.apply_batch)(inp, iss, isl, out, oss, osl, S, n)
+        torch.cuda.synchronize()
+        return plan, out
+
+    try:
+        for name, n, p, S, ip, acc, k in cases:
+            key = (name, n, p, S, ip, acc)
+            if key not in refs:  # the default shape's output, computed once per layout
+                knobs("")
+                refs[key] = run(*key)[1]
+            knobs(k)
+            plan, out = run(*key)
+            assert plan and ecx.last_launch_shape() == plan, (name, n, p, S, ip, acc, k, plan, ecx.last_launch_shape())
+            assert torch.equal(out, refs[key]), (name, n, p, S, ip, acc, k, plan)
+            families.add(plan.split("<")[0].split(" ")[0])
+    finally:
+        rec.set_knob(ecx, "")
+    assert families >= want, want - families
+
+
+def test_launch_plan_names_what_runs(ecx, torch_dev):
+    """The launch rules asked without a device (GfMap.launch_plan, csrc/launch_rules.cpp) name
+    exactly what the instance tables then launch: for 35 (map, layout, knob) cases that reach
+    every kernel family of the product library -- k_gf_apply on 256 threads and on one wave, its
+    small-row, LDS-table, depth-2 and deep-ring instances, k_gf_apply_tail, the wide tiles, the
+    skewed chunks and k_map_planes -- ecx.last_launch_shape() after the real launch equals the
+    plan, and the output equals the default shape's.  Three stripes of at most 64 KiB shards,
+    and one stripe at a 4 MiB pitch (the skew's auto rule).  The lab kernels:
+    test_launch_plan_names_what_runs_diag."""
+    cases = [
+        ("rs124_dec01", 8208, "r16", 3, 0, 0, ""), ("rs124_dec01", 65536, "r16", 3, 1, 0, ""),
+        ("rs124_dec01", 65536, "4m", 1, 1, 0, ""), ("rs173_enc", 8208, "r16", 3, 1, 0, ""),
+        ("rs173_enc", 65536, "pad", 3, 0, 1, ""), ("lrc_rep0", 65536, "r16", 3, 1, 0, ""),
+        ("rs124_dec01", 4000, "r16", 3, 0, 0, ""), ("lrc_enc", 16384, "r16", 3, 1, 0, ""),
+        ("clay42_rep1", 65536, "r16", 3, 0, 0, ""),
+        ("clay42_rep03", 65536, "r16", 3, 0, 0, ""), ("clay42_enc45", 8208, "pad", 3, 0, 1, ""),
+        ("partial1", 8176, "r16", 3, 0, 1, ""),
+        ("rs173_enc", 65536, "r16", 3, 1, 0, "depth=2"), ("lrc_rep0", 65536, "r16", 3, 1, 0, "depth=12"),
+        ("clay42_rep1", 65536, "r16", 3, 0, 0, "depth=24"), ("rs173_enc", 8208, "r16", 3, 1, 0, "nontemporal=0"),
+        ("clay42_rep03", 65536, "r16", 3, 0, 0, "nontemporal=2"), ("clay42_rep1", 65536, "r16", 3, 0, 0, "store_scope=1"),
+        ("lrc_rep0", 65536, "r16", 3, 1, 0, "small_tiles=0"), ("rs173_enc", 65536, "r16", 3, 1, 0, "small_tiles=1"),
+        ("clay42_rep03", 65536, "r16", 3, 0, 0, "wide_tiles=0"), ("rs173_enc", 65536, "r16", 3, 1, 0, "lds_tables=2"),
+        ("clay42_enc45", 65536, "r16", 3, 0, 0, "lds_tables=0"), ("rs173_enc", 8208, "r16", 3, 1, 0, "block_threads=64"),
+        ("rs124_dec01", 8208, "r16", 3, 1, 0, "block_threads=256"), ("rs173_enc", 65536, "r16", 3, 1, 0, "skew_chunks=2"),
+        ("rs124_dec01", 65536, "r16", 3, 1, 0, "block_threads=256,skew_chunks=4"), ("clay42_rep1", 65536, "r16", 3, 0, 0, "skew_chunks=2"),
+        ("rs173_enc", 8208, "r16", 3, 1, 0, "skew_chunks=2"), ("rs173_enc", 65536, "r16", 3, 1, 0, "xcd_group=3"),
+        ("rs124_dec01", 65536, "r16", 3, 1, 0, "stagger=2"), ("rs173_enc", 65536, "r16", 3, 1, 0, "chunk_major=1"),
+        ("clay42_rep03", 65536, "r16", 3, 0, 0, "map_planes=2"), ("rs173_enc", 8208, "r16", 3, 1, 1, "map_planes=2"),
+    ]
+    _plans_name_what_runs(ecx, torch_dev, cases,
+                          {"k_gf_apply", "k_gf_apply_tail", "k_gf_apply_wide", "k_gf_apply_skew", "k_map_planes"})
+
+
+@pytest.mark.diag
+def test_launch_plan_names_what_runs_diag(ecx, torch_dev):
+    """As test_launch_plan_names_what_runs, for the kernels only the diagnostic library holds:
+    the tile groups (LDS-staged and direct), k_gf_bits, k_gf_lut in both modes, k_gf_apply_multi
+    with and without the fused tail, the residency cap and the one-wave skew."""
+    cases = [
+        ("clay42_enc45", 8208, "r16", 3, 0, 0, "wave_groups=1"), ("clay42_enc45", 65536, "r16", 3, 0, 0, "wave_groups=2"),
+        ("rs173_enc", 8208, "r16", 3, 1, 0, "bitslice=2"), ("clay42_rep03", 65536, "r16", 3, 0, 0, "bitslice=2"),
+        ("rs173_enc", 8208, "r16", 3, 1, 0, "lds_lut=1"), ("rs124_dec01", 65536, "r16", 3, 1, 0, "lds_lut=2"),
+        ("rs173_enc", 8208, "r16", 3, 1, 0, "units=2"), ("rs124_dec01", 65536, "r16", 3, 1, 0, "units=4"),
+        ("rs124_dec01", 65536, "r16", 3, 1, 0, "occ_lds=-1"), ("rs124_dec01", 65536, "r16", 3, 1, 0, "block_threads=64,skew_chunks=4"),
+    ]
+    _plans_name_what_runs(ecx, torch_dev, cases,
+                          {"k_gf_apply_lds", "k_gf_apply_grp", "k_gf_bits", "k_gf_lut", "k_gf_apply_multi",
+                           "k_gf_apply_skew", "k_gf_apply"})
+
+
+@pytest.mark.diag
+def test_launch_plan_reproduces_recorded_shapes_diag(ecx):
+    """The diagnostic library's half of tests/golden/launch_shapes.jsonl.gz (`diag`: 1, recorded
+    from the diagnostic library as it was before the launch rules became a unit of their own),
+    replayed through GfMap.launch_plan as tests/test_planner.py replays the product library's:
+    ecx_map_launch_plan answers for the build it is in, so only this library can check them."""
+    rec = _recorder()
+    lines = rec.read_lines(GOLDEN / "launch_shapes.jsonl.gz")
+    n = sum(1 for r in lines if r["diag"] == 1)
+    assert n > 1000 and rec.replay(ecx, lines) == n

@@ -45,3 +45,26 @@ def test_host_executor_under_asan_ubsan(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     assert "host_exec_check: ok" in r.stdout
     assert "isa 2: not on this CPU" not in r.stdout or "isa 1: not on this CPU" not in r.stdout
+
+
+@pytest.mark.timeout(300)
+def test_launch_rules_invariants_under_asan_ubsan(tmp_path):
+    """The launch rules (csrc/launch_rules.cpp: which kernels a batch launches, in what shape) are
+    plain C++ with no HIP header: built here from that one file, with no ROCm include path, and
+    walked over a dense grid of synthetic map traits x batch layouts x knobs by
+    tests/native/launch_rules_check.cpp, which asserts for every plan that the launches tile the
+    shard's chunks exactly once, that only byte-safe launches touch bytes outside full aligned
+    chunks (but for a fused tail, and that only when no output is read), and that no kernel is
+    chosen on a layout it cannot address."""
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "launch_rules_check"
+    srcs = [ROOT / "tests" / "native" / "launch_rules_check.cpp",
+            ROOT / "repair-pipelining_amd" / "csrc" / "launch_rules.cpp"]
+    subprocess.run([gxx, "-std=c++17", "-O2", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-omit-frame-pointer", "-fno-sanitize-recover=all", "-o", str(exe)] + [str(s) for s in srcs],
+                   check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "launch_rules_check: ok" in r.stdout

@@ -570,3 +570,58 @@ def test_clay_is_test_branch_parity_row_throws(ecx, k, m, e):
         O.Clay(k, m, [e], is_test=True).perform_coding(inputs, [np.zeros(8, np.uint8) for _ in range(a)], 8)
     assert "-6" in str(eo.value) or "Null" in str(eo.value)
     assert ecx.ClayCodeErasureDecodingStep([e], k, m).map() is not None
+
+
+# ---------------------------------------------------------------- launch rules (csrc/launch_rules.cpp)
+def load_recorder():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("record_launch_shapes", ROOT / "scripts" / "record_launch_shapes.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_launch_plan_reproduces_recorded_shapes(ecx):
+    """tests/golden/launch_shapes.jsonl.gz holds, for the full grid of maps, batch layouts and
+    knobs, the string ecx_last_launch_shape reported after the real launch on an MI355X, recorded
+    by scripts/record_launch_shapes.py from the library as it was before the launch rules became
+    a unit of their own.  The rules, asked without a device (GfMap.launch_plan), must give every
+    one of them (record_launch_shapes.replay: lines are in launch order, and a call with no kernel
+    of record leaves the string of the line before it).  ecx_map_launch_plan answers for the
+    build it is in, so the product library's lines are checked here and the diagnostic library's
+    by tests/test_gpu_parity.py::test_launch_plan_reproduces_recorded_shapes_diag, which the
+    `gpu and diag` run of that library selects (it also runs here when that library is loaded)."""
+    rec = load_recorder()
+    lines = rec.read_lines(ROOT / "tests" / "golden" / "launch_shapes.jsonl.gz")
+    n = {d: sum(1 for r in lines if r["diag"] == d) for d in (0, 1)}
+    assert n[0] > 10000 and n[1] > 1000 and n[0] + n[1] == len(lines)
+    assert rec.replay(ecx, lines) == n[int(ecx.is_diag())]
+
+
+def test_launch_plan_names_every_profiled_candidate(ecx):
+    """profiles/pmc_traffic.json keys the rs124 and rs173 traffic profiles by the launch shape of
+    each "layout_select" candidate (by_shape), each taken with the knobs that force that candidate
+    (scripts/pmc.sh CAND_TUNES, kept in the entry's `tune`).  The rules must plan exactly that
+    name for that workload's layout (bench.py RS124 / RS173: in place, [pool][shards][pitch])
+    and that candidate index; candidate 0, the static rules, is the workload's own entry."""
+    import json
+    import bench
+    cand_of = {("block_threads=256", "skew_chunks=0"): 1, ("block_threads=256", "skew_chunks=4"): 2,
+               ("block_threads=64", "skew_chunks=0"): 3, ("block_threads=64", "skew_chunks=0", "stagger=2"): 4,
+               ("block_threads=64", "skew_chunks=0", "stagger=8"): 5,
+               ("block_threads=256", "skew_chunks=0", "stagger=4"): 6}
+    prof = json.loads((ROOT / "profiles" / "pmc_traffic.json").read_text())["workloads"]
+    rs124, rs173 = ecx.ReedSolomon.create(12, 4), ecx.ReedSolomon.create(17, 3)
+    work = {"rs124": (rs124.decode_map([False, False] + [True] * 14), bench.RS124.n, bench.RS124.L),
+            "rs173": (rs173.encode_map(), bench.RS173.n, bench.RS173.L)}
+    for w, (gmap, shards, L) in work.items():
+        pool = prof[w]["pool_stripes"]
+        base = 1 << 40
+        plans = [gmap.launch_plan(base, shards * L, L, base, shards * L, L, pool, L, False, c) for c in range(7)]
+        seen = set()
+        for name, entry in prof[w]["by_shape"].items():
+            c = cand_of[tuple(entry["tune"])]
+            assert plans[c] == name == entry["launch_shape"], (w, c, plans[c], name)
+            seen.add(c)
+        assert seen == set(range(1, 7)), (w, seen)
+        assert plans[0] in prof[w]["by_shape"], (w, plans[0])  # the static rules' shape is one of the six
