@@ -15,6 +15,7 @@
 // it keeps every load a full 16-B access (byte counts that are multiples of 16 on aligned
 // layouts; otherwise a byte-safe launch covers the remainder).
 #include "apply.hpp"
+#include "layout_probe.hpp"  // note_device_launch
 
 namespace ecx {
 

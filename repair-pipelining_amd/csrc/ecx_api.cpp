@@ -18,6 +18,7 @@
 #include "map_rtc.hpp"
 #include "engine.hpp"
 #include "host_pipe.hpp"
+#include "layout_probe.hpp"  // note_device_launch
 
 using namespace ecx;
 

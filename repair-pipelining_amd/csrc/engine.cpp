@@ -447,13 +447,6 @@ const uint8_t *zero_page_for_current_device() {
 }
 
 CompiledMap::~CompiledMap() {
-    for (auto &kv : layout_sel_) {
-        for (auto &p : kv.second.pending) {
-            if (p.e1) close_probe(p.dev, p.e1);
-            if (p.e0) (void)hipEventDestroy(p.e0);
-            if (p.e1) (void)hipEventDestroy(p.e1);
-        }
-    }
     for (auto &kv : dev_) {
         int cur = 0;
         if (hipGetDevice(&cur) != hipSuccess) continue;
@@ -711,285 +704,6 @@ MapPlanes *CompiledMap::planes() {
         if (map_planes_supported(map_)) planes_ = std::make_unique<MapPlanes>(map_);
     }
     return planes_.get();
-}
-
-namespace {
-constexpr float kLayoutMargin = 0.98f;   // another shape replaces the static rules' only if 2 % faster
-constexpr size_t kMaxLayouts = 64;       // layouts selected per map; past that, new ones use the static rules
-constexpr int kLayoutMaxDropped = 64;    // contaminated probes before a layout is declared contended
-constexpr int64_t kLayoutRevalidate = 512;  // launches after a choice before its one re-validation
-
-float median_of(std::vector<float> v) {
-    std::sort(v.begin(), v.end());
-    return v.empty() ? -1.f : v[v.size() / 2];
-}
-
-// A filled layout probe still open to contamination: until a launch on another stream of its
-// device finds its end event done, such a launch may share the GPU with it (`dirty`).
-struct OpenProbe {
-    hipStream_t stream;
-    hipEvent_t e1;
-    std::shared_ptr<std::atomic<bool>> dirty;
-};
-// A stream's launches: the latest one's serial, and an event recorded behind its latest LARGE
-// launch (>= kMarkBytes of input), so a probe can tell whether one may still run.  A smaller
-// launch runs for microseconds, negligible against a multi-millisecond probe, and is not marked.
-struct StreamMark {
-    uint64_t serial = 0;
-    hipEvent_t done = nullptr;
-    bool marked = false;  // `done` was recorded behind a large launch of this stream
-};
-constexpr int64_t kMarkBytes = 64 << 20;
-constexpr uint64_t kUnmarkedLarge = 1ull << 63;  // serial flag: a large launch whose event failed
-struct DevLaunches {
-    uint64_t serial = 0;
-    std::map<hipStream_t, StreamMark> last;  // aged out, below
-    std::vector<OpenProbe> open;
-};
-constexpr uint64_t kStreamAge = 4096;  // a stream silent for this many launches leaves `last`
-std::mutex g_launch_mu;
-std::map<int, DevLaunches> g_launches;
-}  // namespace
-
-uint64_t note_device_launch(int dev, hipStream_t s, int64_t bytes) {
-    std::lock_guard<std::mutex> lk(g_launch_mu);
-    DevLaunches &d = g_launches[dev];
-    StreamMark &mk = d.last[s];
-    mk.serial = ++d.serial;
-    if (bytes >= kMarkBytes) {
-        if (!mk.done && hipEventCreateWithFlags(&mk.done, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            mk.done = nullptr;
-        }
-        // unmarked when the record fails: this large launch then counts as possibly running
-        mk.marked = mk.done && hipEventRecord(mk.done, s) == hipSuccess;
-        if (!mk.marked) {
-            (void)hipGetLastError();
-            mk.serial |= kUnmarkedLarge;
-        }
-    }
-    // An open probe on another stream, at a large launch: still running -> this launch may
-    // overlap it (dirty); finished -> no later launch can, so its window closes here.  Either way
-    // it leaves the list.
-    for (auto it = d.open.begin(); bytes >= kMarkBytes && it != d.open.end();) {
-        if (it->stream == s) {  // same stream: queued behind the probe
-            ++it;
-            continue;
-        }
-        const hipError_t q = hipEventQuery(it->e1);
-        if (q == hipErrorNotReady) it->dirty->store(true);
-        else if (q != hipSuccess) (void)hipGetLastError();
-        it = d.open.erase(it);
-    }
-    if (d.serial % 256 == 0)  // bounded: streams not seen for kStreamAge launches are forgotten
-        for (auto it = d.last.begin(); it != d.last.end();) {
-            if ((it->second.serial & ~kUnmarkedLarge) + kStreamAge >= d.serial) {
-                ++it;
-                continue;
-            }
-            if (it->second.done) (void)hipEventDestroy(it->second.done);
-            it = d.last.erase(it);
-        }
-    return d.serial;
-}
-
-uint64_t stream_last_launch(int dev, hipStream_t s) {
-    std::lock_guard<std::mutex> lk(g_launch_mu);
-    auto it = g_launches.find(dev);
-    if (it == g_launches.end()) return 0;
-    auto jt = it->second.last.find(s);
-    return jt == it->second.last.end() ? 0 : jt->second.serial & ~kUnmarkedLarge;
-}
-
-bool other_stream_may_run(int dev, hipStream_t s, uint64_t since) {
-    std::lock_guard<std::mutex> lk(g_launch_mu);
-    auto it = g_launches.find(dev);
-    if (it == g_launches.end()) return false;
-    for (const auto &kv : it->second.last) {
-        if (kv.first == s) continue;
-        const StreamMark &mk = kv.second;
-        if (mk.serial & kUnmarkedLarge) {  // a large launch without an event: assume it may run
-            if ((mk.serial & ~kUnmarkedLarge) > since) return true;
-        } else if (mk.marked) {  // its latest large launch: running iff the event is not done
-            const hipError_t q = hipEventQuery(mk.done);
-            if (q == hipErrorNotReady) return true;
-            if (q != hipSuccess) (void)hipGetLastError();
-        }
-    }
-    return false;
-}
-
-std::shared_ptr<std::atomic<bool>> open_probe(int dev, hipStream_t s, hipEvent_t e1, bool dirty) {
-    auto flag = std::make_shared<std::atomic<bool>>(dirty);
-    std::lock_guard<std::mutex> lk(g_launch_mu);
-    if (!dirty) g_launches[dev].open.push_back({s, e1, flag});
-    return flag;
-}
-
-void close_probe(int dev, hipEvent_t e1) {
-    std::lock_guard<std::mutex> lk(g_launch_mu);
-    auto it = g_launches.find(dev);
-    if (it == g_launches.end()) return;
-    auto &v = it->second.open;
-    for (auto jt = v.begin(); jt != v.end(); ++jt)
-        if (jt->e1 == e1) {
-            v.erase(jt);
-            return;
-        }
-}
-
-// Reads the finished probes of `s` (non-blocking): clean timings go to the exploration's
-// per-candidate lists, or to the re-validation's pair; contaminated ones are counted and dropped.
-void CompiledMap::harvest(LayoutSel &s, int n_cand) {
-    for (auto it = s.pending.begin(); it != s.pending.end();) {
-        if (!it->e1) {  // reserved, not yet launched
-            ++it;
-            continue;
-        }
-        const hipError_t q = hipEventQuery(it->e1);
-        if (q == hipErrorNotReady) {
-            ++it;
-            continue;
-        }
-        float ms = 0.f;
-        const bool timed = q == hipSuccess && hipEventElapsedTime(&ms, it->e0, it->e1) == hipSuccess && ms > 0.f;
-        close_probe(it->dev, it->e1);  // before its events go
-        if (!timed) (void)hipGetLastError();  // a failed probe is dropped; its candidate is timed again
-        else if (it->dirty && it->dirty->load()) ++s.dropped;
-        else if (s.state == kLayoutRevalidating) {
-            if (it->cand == s.reval_alt) s.reval_ms[0].push_back(ms);
-            else if (it->cand == s.chosen) s.reval_ms[1].push_back(ms);
-        } else if (s.state == kLayoutExploring && it->cand < n_cand) {
-            s.ms[it->cand].push_back(ms);
-        }
-        (void)hipEventDestroy(it->e0);
-        (void)hipEventDestroy(it->e1);
-        it = s.pending.erase(it);
-    }
-}
-
-int CompiledMap::next_layout_pick(const std::array<int64_t, 8> &key, int n_cand, int samples, int dev,
-                                  hipStream_t stream, uint64_t *ticket) {
-    std::lock_guard<std::mutex> lk(mu_);
-    *ticket = 0;
-    const bool fresh = !layout_sel_.count(key);
-    if (fresh && layout_sel_.size() >= kMaxLayouts) return 0;  // bounded: the static rules
-    LayoutSel &s = layout_sel_[key];
-    if ((int)s.ms.size() != n_cand) s.ms.assign(n_cand, {});
-    harvest(s, n_cand);  // also after the choice, so late probes free their events
-    auto reserve = [&](int cand) {
-        *ticket = ++ticket_serial_;
-        s.pending.push_back({cand, nullptr, nullptr, *ticket, dev, stream, stream_last_launch(dev, stream), nullptr});
-        return cand;
-    };
-    auto in_flight = [&](int cand) {
-        int n = 0;
-        for (const auto &p : s.pending) n += p.cand == cand;
-        return n;
-    };
-    if (s.state == kLayoutContended || s.state == kLayoutRevalidated) return s.chosen;
-    if (s.state == kLayoutChosen) {
-        if (s.chosen == s.reval_alt || ++s.steady < kLayoutRevalidate) return s.chosen;
-        s.state = kLayoutRevalidating;  // once: the kept shape against its alternative, clean timings
-    }
-    if (s.dropped >= kLayoutMaxDropped) {
-        // another stream keeps the device busy while probes run: no timing here is trustworthy
-        s.chosen = 0;
-        s.state = kLayoutContended;
-        s.serial = ++layout_serial_;
-        return 0;
-    }
-    if (s.state == kLayoutRevalidating) {
-        const int have[2] = {(int)s.reval_ms[0].size() + in_flight(s.reval_alt),
-                             (int)s.reval_ms[1].size() + in_flight(s.chosen)};
-        if ((int)s.reval_ms[0].size() >= samples && (int)s.reval_ms[1].size() >= samples) {
-            const float alt = median_of(s.reval_ms[0]), kept = median_of(s.reval_ms[1]);
-            // a shape other than the static rules (candidate 0) must keep beating them by the margin;
-            // a kept static choice is replaced only by a runner-up that beats it by the margin
-            const bool keep = s.reval_alt == 0 ? kept < kLayoutMargin * alt : !(alt < kLayoutMargin * kept);
-            if (!keep) s.chosen = s.reval_alt;
-            s.state = kLayoutRevalidated;
-            s.serial = ++layout_serial_;
-                return s.chosen;
-        }
-        if (have[0] >= samples && have[1] >= samples) return s.chosen;  // all in flight: untimed
-        return reserve(have[0] <= have[1] ? s.reval_alt : s.chosen);
-    }
-    // exploring
-    std::vector<int> queued(n_cand, 0);
-    bool done = true;
-    for (int c = 0; c < n_cand; ++c) {
-        queued[c] = (int)s.ms[c].size();
-        done = done && queued[c] >= samples;
-    }
-    if (done) {
-        const float base = median_of(s.ms[0]);
-        int best = 0, second = -1;
-        float best_ms = base;
-        for (int c = 1; c < n_cand; ++c) {
-            const float m = median_of(s.ms[c]);
-            if (m < best_ms && m < kLayoutMargin * base) {
-                best = c;
-                best_ms = m;
-            }
-        }
-        for (int c = 0; c < n_cand; ++c)  // the runner-up: what a kept static choice is re-checked against
-            if (c != best && (second < 0 || median_of(s.ms[c]) < median_of(s.ms[second]))) second = c;
-        s.chosen = best;
-        s.reval_alt = best != 0 ? 0 : (second >= 0 ? second : 0);
-        s.state = kLayoutChosen;
-        s.steady = 0;
-        s.serial = ++layout_serial_;
-        return best;
-    }
-    for (const auto &p : s.pending) ++queued[p.cand];
-    int c = 0;
-    for (int k = 1; k < n_cand; ++k)
-        if (queued[k] < queued[c]) c = k;
-    if (queued[c] >= samples) return 0;  // every probe is in flight: the static rules, untimed
-    return reserve(c);
-}
-
-void CompiledMap::fill_layout_probe(const std::array<int64_t, 8> &key, uint64_t ticket, hipEvent_t e0,
-                                    hipEvent_t e1) {
-    std::lock_guard<std::mutex> lk(mu_);
-    for (auto &p : layout_sel_[key].pending)
-        if (p.ticket == ticket) {
-            p.e0 = e0;
-            p.e1 = e1;
-            // contaminated already if another stream's latest launch may still run as the probe
-            // is enqueued; later launches are judged by note_device_launch while it is open
-            p.dirty = open_probe(p.dev, p.stream, e1, other_stream_may_run(p.dev, p.stream, p.since));
-            return;
-        }
-    (void)hipEventDestroy(e0);  // not reserved (cannot happen): drop the events
-    (void)hipEventDestroy(e1);
-}
-
-void CompiledMap::cancel_layout_probe(const std::array<int64_t, 8> &key, uint64_t ticket) {
-    std::lock_guard<std::mutex> lk(mu_);
-    auto &v = layout_sel_[key].pending;
-    for (auto it = v.begin(); it != v.end(); ++it)
-        if (it->ticket == ticket) {
-            v.erase(it);
-            return;
-        }
-}
-
-int CompiledMap::layout_choice(int64_t pitch, std::vector<float> *ms, int *state, int *dropped) {
-    std::lock_guard<std::mutex> lk(mu_);
-    const LayoutSel *latest = nullptr;
-    for (const auto &kv : layout_sel_)
-        if (kv.first[0] == pitch && kv.second.chosen >= 0 && (!latest || kv.second.serial > latest->serial))
-            latest = &kv.second;
-    if (!latest) return -1;
-    if (ms) {
-        ms->clear();
-        for (const auto &v : latest->ms) ms->push_back(median_of(v));
-    }
-    if (state) *state = latest->state;
-    if (dropped) *dropped = latest->dropped;
-    return latest->chosen;
 }
 
 const std::vector<int> &CompiledMap::used_in_slots() {

@@ -35,6 +35,7 @@
 #include "codes.hpp"
 #include "host_exec.hpp"
 #include "launch_rules.hpp"  // the shape constants (kTileRows, kChunkBytes, ...), Tuning, MapTraits
+#include "layout_probe.hpp"  // LayoutSelection
 
 namespace ecx {
 
@@ -147,62 +148,19 @@ public:
     MapPlanes *planes();
     const std::vector<int> &used_in_slots();
     const std::vector<int> &used_out_slots();
-    // Per-layout launch-shape selection (kernels.hip launch_apply, ecx_tune "layout_select"):
-    // the candidate to run for this call of the batch layout `key` on `stream` of device `dev`.
-    // Finished timing probes are harvested first (non-blocking).  A probe is DROPPED, not
-    // counted, when another stream of the same device had a large libecx launch that may still
-    // run when the probe was enqueued, or enqueued one while the probe was still running (the
-    // first such launch that finds the probe's end event done closes its window;
-    // note_device_launch): that kernel may have shared the GPU with the probe.  Once every
-    // one of the n_cand candidates has `samples` clean
-    // timings the fastest median is kept (candidate 0 -- the static rules -- unless another is
-    // faster by kLayoutMargin); after kLayoutMaxDropped dropped probes the layout is CONTENDED
-    // and keeps candidate 0 untimed.  Any kept shape is re-validated once, after
-    // kLayoutRevalidate further launches, against its alternative -- the static rules for a
-    // non-static choice, the runner-up for a static one: `samples` clean timings of each, and
-    // the alternative takes over if it wins by the margin (a non-static choice must keep
-    // beating the static rules by it).  At most kMaxLayouts layouts are selected per map (later ones get candidate 0,
-    // untimed).  When the call is to be timed, *ticket is set to a non-zero probe slot
-    // reserved in the layout's pending list (so concurrent callers are never handed the same
-    // probe twice): the caller brackets its launch with two events on `stream` and hands them
-    // to fill_layout_probe, or gives the slot back with cancel_layout_probe.
-    int next_layout_pick(const std::array<int64_t, 8> &key, int n_cand, int samples, int dev, hipStream_t stream,
-                         uint64_t *ticket);
-    void fill_layout_probe(const std::array<int64_t, 8> &key, uint64_t ticket, hipEvent_t e0, hipEvent_t e1);
-    void cancel_layout_probe(const std::array<int64_t, 8> &key, uint64_t ticket);
+    // The per-layout launch-shape selection of this map (kernels.hip launch_apply, ecx_tune
+    // "layout_select"; layout_select.hpp has the rules).
+    LayoutSelection &layout_selection() { return layout_; }
     // The candidate kept for the most recently selected layout with input slot pitch
     // `pitch`, -1 if none yet; with `ms`, the per-candidate median launch times (ms, -1 =
     // unsampled) of that layout; with `state` its state (LayoutState) and with `dropped` the
-    // probes it dropped as contaminated.
-    int layout_choice(int64_t pitch, std::vector<float> *ms = nullptr, int *state = nullptr, int *dropped = nullptr);
-    enum LayoutState { kLayoutExploring = 0, kLayoutChosen = 1, kLayoutRevalidating = 2, kLayoutRevalidated = 3,
-                       kLayoutContended = 4 };
+    // timings it dropped as contaminated.
+    int layout_choice(int64_t pitch, std::vector<float> *ms = nullptr, int *state = nullptr, int *dropped = nullptr) {
+        return layout_.choice(pitch, ms, state, dropped);
+    }
 
 private:
-    struct LayoutSel {
-        struct Probe {
-            int cand;
-            hipEvent_t e0, e1;   // null until fill_layout_probe
-            uint64_t ticket;
-            int dev;
-            hipStream_t stream;
-            uint64_t since;      // the stream's last launch serial before this probe (note_device_launch)
-            std::shared_ptr<std::atomic<bool>> dirty;  // set when another stream's launch may overlap it
-        };
-        std::vector<std::vector<float>> ms;  // per candidate: clean launch times of its probes
-        std::vector<Probe> pending;          // reserved or unfinished probes
-        int chosen = -1;
-        int state = kLayoutExploring;
-        int dropped = 0;                     // probes discarded as contaminated
-        int64_t steady = 0;                  // launches since the choice (re-validation trigger)
-        int reval_alt = 0;                   // the shape the kept one is re-validated against
-        std::vector<float> reval_ms[2];      // re-validation timings: [0] the alternative, [1] the kept shape
-        uint64_t serial = 0;                 // order of the choices (layout_choice reports the latest)
-    };
-    void harvest(LayoutSel &s, int n_cand);
-    std::map<std::array<int64_t, 8>, LayoutSel> layout_sel_;
-    uint64_t layout_serial_ = 0;
-    uint64_t ticket_serial_ = 0;
+    LayoutSelection layout_;
     LinearMap map_;
     std::unique_ptr<CompiledMap> compact_;
     std::unique_ptr<MapPlanes> planes_;
@@ -278,23 +236,6 @@ void note_kernel(const char *name, P... params) {
     s += '>';
     set_last_kernel(std::move(s));
 }
-
-// Per-device launch registry (engine.cpp), read by the layout selection's contamination check:
-// every batch launch of the library (launch_apply, launch_check, the generated Clay kernels)
-// records its stream and input bytes here.  note_device_launch returns the launch's serial and,
-// for a launch of >= 64 MiB, records an event behind it (smaller launches run for microseconds
-// and never count as overlapping a probe); stream_last_launch is the serial of a stream's latest
-// launch (0 = none); other_stream_may_run whether a stream other than `s` on device `dev` has a
-// large launch that may still run (its event is not done; or no event could be recorded and it
-// came after `since`).  Streams unseen for 4,096 launches age out of the registry.
-uint64_t note_device_launch(int dev, hipStream_t s, int64_t bytes);
-uint64_t stream_last_launch(int dev, hipStream_t s);
-bool other_stream_may_run(int dev, hipStream_t s, uint64_t since);
-// A layout probe whose end event `e1` is recorded on `s`: registered (unless already `dirty`)
-// so that note_device_launch on another stream of `dev` flags it while it runs; close_probe
-// unregisters it before its events are destroyed.
-std::shared_ptr<std::atomic<bool>> open_probe(int dev, hipStream_t s, hipEvent_t e1, bool dirty);
-void close_probe(int dev, hipEvent_t e1);
 
 // Enqueue out = M * in over nstripes stripes (kernels.hip); which kernels run, and in what
 // shape, is decided by launch_rules.hpp choose_launch.

@@ -17,6 +17,7 @@
 //     coefficient 1 is a bare XOR (LRC local parity);
 //   * no LDS, no MFMA: this is HBM-bound byte work.
 #include "apply.hpp"
+#include "layout_probe.hpp"
 #include "map_rtc.hpp"
 
 namespace ecx {
@@ -395,13 +396,11 @@ void launch_apply_core(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_str
 // new layout (map, strides, size classes of the shard and the batch, device) the first calls run the
 // candidates in turn, each launch bracketed by two events on the caller's stream; the
 // events are read without blocking on later calls, and once every candidate has
-// kLayoutSamples timings the fastest median is kept for that layout.  Every candidate
+// kLayoutSamples timings the fastest median is kept for that layout (layout_select.hpp).  Every candidate
 // computes the same bytes, and nothing is launched that the caller did not ask for: the
 // exploration costs only the slower candidates' launches.  Batches under kLayoutMinBytes of
 // input, streams being captured and forced shapes use the static rules
 // (launch_rules.hpp layout_select_eligible; the candidates are its kLayoutCand).
-constexpr int kLayoutSamples = 5;  // median of 5: 3 left a 2-5 % spread between fresh maps (scripts/select_check.py)
-
 void launch_apply(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_stride, int64_t in_slot_stride, uint8_t *out,
                   int64_t out_stripe_stride, int64_t out_slot_stride, int64_t nstripes, int64_t nbytes,
                   hipStream_t stream, bool accumulate) {
@@ -429,43 +428,13 @@ void launch_apply(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_stride, 
     // batch (log2 of its input bytes), the mode and the device: callers whose batch sizes vary
     // from call to call share one selection instead of exploring anew at every size.
     auto log2i = [](int64_t v) { return (int64_t)(63 - __builtin_clzll((unsigned long long)std::max<int64_t>(v, 1))); };
-    const std::array<int64_t, 8> key{in_slot_stride, in_stripe_stride, out_slot_stride, out_stripe_stride,
-                                     log2i(nbytes), log2i(nstripes * in_bytes), (int64_t)accumulate, (int64_t)dev};
-    uint64_t ticket = 0;
-    const int cand = cm.next_layout_pick(key, kLayoutNCand, kLayoutSamples, dev, stream, &ticket);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ticket) {
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-            (void)hipGetLastError();
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-            e0 = e1 = nullptr;
-            cm.cancel_layout_probe(key, ticket);
-            ticket = 0;
-        }
-    }
-    try {
-        launch_apply_core(cm, in, in_stripe_stride, in_slot_stride, out, out_stripe_stride, out_slot_stride, nstripes,
-                          nbytes, stream, accumulate, kLayoutCand[cand], ticket ? e0 : nullptr);
-    } catch (...) {
-        if (ticket) {
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-            cm.cancel_layout_probe(key, ticket);
-        }
-        throw;
-    }
+    const LayoutKey key{in_slot_stride, in_stripe_stride, out_slot_stride, out_stripe_stride,
+                        log2i(nbytes), log2i(nstripes * in_bytes), (int64_t)accumulate, (int64_t)dev};
+    ProbeGuard probe(cm.layout_selection(), key, dev, stream);
+    launch_apply_core(cm, in, in_stripe_stride, in_slot_stride, out, out_stripe_stride, out_slot_stride, nstripes,
+                      nbytes, stream, accumulate, kLayoutCand[probe.cand()], probe.start());
     note_device_launch(dev, stream, nstripes * in_bytes);
-    if (ticket) {
-        if (hipEventRecord(e1, stream) == hipSuccess) {
-            cm.fill_layout_probe(key, ticket, e0, e1);
-        } else {
-            (void)hipGetLastError();
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-            cm.cancel_layout_probe(key, ticket);
-        }
-    }
+    probe.finish();
 }
 
 // ---------------------------------------------------------------- synthetic data

@@ -68,3 +68,30 @@ def test_launch_rules_invariants_under_asan_ubsan(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "launch_rules_check: ok" in r.stdout
+
+
+@pytest.mark.timeout(300)
+def test_layout_selection_rules_and_recorded_trace_under_asan_ubsan(tmp_path):
+    """The per-layout launch-shape decisions (csrc/layout_select.cpp: which candidate a call runs,
+    when it is timed, what is kept) are plain C++ with no HIP header: built here from that one file,
+    with no ROCm include path, and driven by tests/native/layout_select_check.cpp -- seeded random
+    scripts of picks, reports (clean, contaminated, failed) and cancels with the selection's
+    invariants asserted after every operation, then tests/golden/layout_trace.txt.gz, the decisions
+    recorded by scripts/record_layout_trace.py from the code the table was split out of, replayed
+    line for line."""
+    import gzip
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "layout_select_check"
+    srcs = [ROOT / "tests" / "native" / "layout_select_check.cpp",
+            ROOT / "repair-pipelining_amd" / "csrc" / "layout_select.cpp"]
+    subprocess.run([gxx, "-std=c++17", "-O2", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-omit-frame-pointer", "-fno-sanitize-recover=all", "-o", str(exe)] + [str(s) for s in srcs],
+                   check=True)
+    trace = tmp_path / "layout_trace.txt"
+    trace.write_bytes(gzip.decompress((ROOT / "tests" / "golden" / "layout_trace.txt.gz").read_bytes()))
+    r = subprocess.run([str(exe), str(trace)], capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "layout_select_check: ok" in r.stdout
+    assert f"{len(trace.read_text().splitlines())} trace lines replayed" in r.stdout
