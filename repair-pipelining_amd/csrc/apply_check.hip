@@ -78,6 +78,16 @@ __global__ void __launch_bounds__(kBlockThreads, ROWS < kTileRows ? (DEPTH >= 16
     }
 }
 
+// verdict[s] = 1 for every stripe, ahead of the check's launches.  A kernel, not hipMemsetAsync:
+// on a capturing stream a memset becomes a memset node, and the HIP runtime (ROCm 7.0) replays a
+// memset node with the value 0 from its second replay on, in every graph of a process but the
+// first one instantiated -- a graph of the memset alone shows it -- so a replayed check reported
+// every stripe as corrupt (tests/test_gpu_capture.py).  A kernel node keeps its arguments.
+__global__ void __launch_bounds__(256) k_set_verdicts(uint8_t *verdict, int64_t nstripes) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < nstripes) verdict[s] = 1;
+}
+
 namespace {
 template <bool SAFE, int D, int R>
 void launch_check_k(dim3 grid, hipStream_t stream, const ApplyArgs &a) {
@@ -87,6 +97,8 @@ void launch_check_k(dim3 grid, hipStream_t stream, const ApplyArgs &a) {
 }  // namespace
 
 namespace {
+int check_depth(const Tuning &tu) { return tu.depth == 8 || tu.depth == 20 ? tu.depth : 4; }
+
 // Clears verdict[s] when a syndrome byte of stripe s over bytes [0, nbytes) is non-zero (the
 // verdicts were set to 1 by launch_check).
 void launch_check_core(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_stride, int64_t in_slot_stride,
@@ -96,7 +108,7 @@ void launch_check_core(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_str
     // (profiles/r05_check_sweep.jsonl).  Accumulator rows: 4 when every tile has at most 4 (RS with
     // m <= 4), else 8.
     const Tuning &tu = tuning();
-    const int depth = tu.depth == 8 || tu.depth == 20 ? tu.depth : 4;
+    const int depth = check_depth(tu);
     const int rows = cm.max_tile_rows() <= 4 ? 4 : kTileRows;
     const bool aligned = aligned16(in) && in_stripe_stride % 16 == 0 && in_slot_stride % 16 == 0;
     const int64_t full = aligned ? nbytes / kChunkBytes : 0;
@@ -171,7 +183,16 @@ void launch_check_core(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_str
 void launch_check(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_stride, int64_t in_slot_stride,
                   uint8_t *verdict, int64_t nstripes, int64_t nbytes, hipStream_t stream) {
     if (nstripes <= 0) return;
-    check_hip(hipMemsetAsync(verdict, 1, (size_t)nstripes, stream), "hipMemsetAsync (verdicts)");
+    const LaunchStreamScope scope(stream);  // first use of device state is refused under capture (engine.hpp)
+    if (nbytes > 0 && cm.map().n_out != 0) {
+        // the device state of the launches below, resident before anything is enqueued: a first
+        // use refused on a capturing stream leaves no node behind
+        (void)cm.plan_for_current_device(check_depth(tuning()));
+        (void)cm.plan_for_current_device(4);
+        (void)zero_page_for_current_device();
+    }
+    hipLaunchKernelGGL(k_set_verdicts, dim3((unsigned)((nstripes + 255) / 256)), dim3(256), 0, stream, verdict, nstripes);
+    check_hip(hipGetLastError(), "k_set_verdicts launch");
     if (nbytes <= 0 || cm.map().n_out == 0) return;
     const int64_t head = (int64_t)((16 - (uintptr_t)in % 16) % 16);
     if (head > 0 && head < nbytes && in_stripe_stride % 16 == 0 && in_slot_stride % 16 == 0) {

@@ -1152,6 +1152,8 @@ int ecx_clay_perform_coding_batch(ecx_clay *clay, const uint8_t *in, int64_t in_
             in_stripe_stride % 16 == 0 && in_sub_stride % 16 == 0 && out_stripe_stride % 16 == 0 &&
             out_sub_stride % 16 == 0 && in_sub_stride >= 0 && out_sub_stride >= 0) {
             if (ClayRtc *r = clay_rtc(clay)) {
+                // first use of the module, its table or the zero page is refused under capture (engine.hpp)
+                const LaunchStreamScope scope((hipStream_t)stream);
                 // auto: a generated kernel that cannot be compiled or loaded here (no
                 // hiprtc, another target) falls back to the composed map; forced (2) throws
                 RtcShape sh = rtc_current_shape();

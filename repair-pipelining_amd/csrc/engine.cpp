@@ -54,6 +54,25 @@ void check_hip(hipError_t e, const char *what) {
 }
 
 namespace {
+thread_local hipStream_t g_launch_stream = nullptr;  // the caller's stream of this thread's launch
+thread_local bool g_launch_stream_set = false;
+}  // namespace
+LaunchStreamScope::LaunchStreamScope(hipStream_t s) : prev_(g_launch_stream), prev_set_(g_launch_stream_set) {
+    g_launch_stream = s;
+    g_launch_stream_set = true;
+}
+LaunchStreamScope::~LaunchStreamScope() {
+    g_launch_stream = prev_;
+    g_launch_stream_set = prev_set_;
+}
+void refuse_if_capturing(const char *what) {
+    if (g_launch_stream_set && stream_is_capturing(g_launch_stream))
+        throw Error(ECX_E_DEVICE, std::string(what) +
+                                      " is not resident on this device and the stream is being captured: "
+                                      "run the same call once outside the capture");
+}
+
+namespace {
 
 uint32_t pack4(const uint8_t *t) {
     return (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
@@ -438,11 +457,18 @@ const uint8_t *zero_page_for_current_device() {
     int dev = 0;
     check_hip(hipGetDevice(&dev), "hipGetDevice");
     std::lock_guard<std::mutex> lk(mu);
-    uint8_t *&p = pages[dev];
-    if (!p) {
-        check_hip(hipMalloc(&p, 4096), "hipMalloc(zero page)");
-        check_hip(hipMemset(p, 0, 4096), "hipMemset(zero page)");
+    auto it = pages.find(dev);
+    if (it != pages.end()) return it->second;
+    refuse_if_capturing("the zero page");
+    uint8_t *p = nullptr;
+    check_hip(hipMalloc(&p, 4096), "hipMalloc(zero page)");
+    // published only once it holds zeros: a page whose memset failed is freed, never handed out
+    const hipError_t e = hipMemset(p, 0, 4096);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        check_hip(e, "hipMemset(zero page)");
     }
+    pages.emplace(dev, p);
     return p;
 }
 
@@ -655,6 +681,7 @@ const DevicePlan &CompiledMap::plan_for_current_device(int depth) {
     std::lock_guard<std::mutex> lk(mu_);
     auto it = dev_.find({dev, depth});
     if (it != dev_.end()) return it->second;
+    refuse_if_capturing("the map's device plan");
     const HostPlan h = padded_plan(depth);
     DevicePlan p;
     p.max_tile_entries = h.max_tile_entries;

@@ -47,6 +47,29 @@ constexpr uint32_t kNoTile = 0xFFFFFFFFu;
 
 void check_hip(hipError_t e, const char *what);
 
+// Stream capture.  A launcher names the caller's stream for the length of
+// its call (LaunchStreamScope: launch_apply, launch_check, the generated Clay kernels' branch of
+// ecx_clay_perform_coding_batch); the first-use sites -- a map's device plan, the zero page, a
+// generated kernel's module and table -- call refuse_if_capturing before their first HIP call.
+// When the named stream is being captured (or its status cannot be read) that throws
+// ECX_E_DEVICE: an allocation, a blocking copy or a module load does not belong in a capture,
+// and the caller is told to run the same call once outside it.  The stream is only asked on a
+// first use, so a launch whose state is resident pays nothing.  Outside a scope (the host-batch
+// pipelines, which own their streams) nothing is refused.
+// (stream_is_capturing: layout_probe.hpp)
+class LaunchStreamScope {
+public:
+    explicit LaunchStreamScope(hipStream_t s);
+    ~LaunchStreamScope();
+    LaunchStreamScope(const LaunchStreamScope &) = delete;
+    LaunchStreamScope &operator=(const LaunchStreamScope &) = delete;
+
+private:
+    hipStream_t prev_;
+    bool prev_set_;
+};
+void refuse_if_capturing(const char *what);
+
 class MapPlanes;  // map_rtc.hpp
 
 constexpr uint32_t kDummySlot = 0xFFFFFFFFu;  // entry padding: loads the device's zero page

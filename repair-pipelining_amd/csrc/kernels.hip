@@ -404,18 +404,12 @@ void launch_apply_core(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_str
 void launch_apply(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_stride, int64_t in_slot_stride, uint8_t *out,
                   int64_t out_stripe_stride, int64_t out_slot_stride, int64_t nstripes, int64_t nbytes,
                   hipStream_t stream, bool accumulate) {
+    const LaunchStreamScope scope(stream);  // first use of device state is refused under capture (engine.hpp)
     const int64_t in_bytes = (int64_t)cm.map().n_in * nbytes;  // per stripe
     bool select = layout_select_eligible(cm.traits(), tuning(),
                                          BatchLayout{(uintptr_t)in, (uintptr_t)out, in_stripe_stride, in_slot_stride,
                                                      out_stripe_stride, out_slot_stride, nstripes, nbytes, accumulate});
-    if (select) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cap) != hipSuccess) {
-            (void)hipGetLastError();
-            cap = hipStreamCaptureStatusActive;  // unknown: no events
-        }
-        select = cap == hipStreamCaptureStatusNone;
-    }
+    if (select) select = !stream_is_capturing(stream);  // capturing or unknown: no events
     int dev = 0;
     check_hip(hipGetDevice(&dev), "hipGetDevice");
     if (!select) {

@@ -33,12 +33,24 @@ std::mutex g_launch_mu;
 std::map<int, DevLaunches> g_launches;
 }  // namespace
 
+bool stream_is_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;  // unknown: treated as capturing
+    }
+    return cap != hipStreamCaptureStatusNone;
+}
+
 uint64_t note_device_launch(int dev, hipStream_t s, int64_t bytes) {
+    // Only a large launch and the ageing pass make event calls, so only they ask the stream; a
+    // capturing stream then makes none (layout_probe.hpp): its launch is counted, nothing else.
+    const bool large = bytes >= kMarkBytes && !stream_is_capturing(s);
     std::lock_guard<std::mutex> lk(g_launch_mu);
     DevLaunches &d = g_launches[dev];
     StreamMark &mk = d.last[s];
     mk.serial = ++d.serial;
-    if (bytes >= kMarkBytes) {
+    if (large) {
         if (!mk.done && hipEventCreateWithFlags(&mk.done, hipEventDisableTiming) != hipSuccess) {
             (void)hipGetLastError();
             mk.done = nullptr;
@@ -53,7 +65,7 @@ uint64_t note_device_launch(int dev, hipStream_t s, int64_t bytes) {
     // An open probe on another stream, at a large launch: still running -> this launch may
     // overlap it (dirty); finished -> no later launch can, so its window closes here.  Either way
     // it leaves the list.
-    for (auto it = d.open.begin(); bytes >= kMarkBytes && it != d.open.end();) {
+    for (auto it = d.open.begin(); large && it != d.open.end();) {
         if (it->stream == s) {  // same stream: queued behind the probe
             ++it;
             continue;
@@ -63,7 +75,9 @@ uint64_t note_device_launch(int dev, hipStream_t s, int64_t bytes) {
         else if (q != hipSuccess) (void)hipGetLastError();
         it = d.open.erase(it);
     }
-    if (d.serial % 256 == 0)  // bounded: streams not seen for kStreamAge launches are forgotten
+    // bounded: streams not seen for kStreamAge launches are forgotten (their events are destroyed:
+    // not from a capturing stream, which leaves the pass to a later launch)
+    if (d.serial % 256 == 0 && (large || (bytes < kMarkBytes && !stream_is_capturing(s))))
         for (auto it = d.last.begin(); it != d.last.end();) {
             if ((it->second.serial & ~kUnmarkedLarge) + kStreamAge >= d.serial) {
                 ++it;

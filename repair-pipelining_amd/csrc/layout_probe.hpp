@@ -24,6 +24,12 @@ namespace ecx {
 // launch (0 = none); other_stream_may_run whether a stream other than `s` on device `dev` has a
 // large launch that may still run (its event is not done; or no event could be recorded and it
 // came after `since`).  Streams unseen for 4,096 launches age out of the registry.
+// A launch on a stream that is being captured (or whose capture status cannot be read) makes no
+// event call at all: a record would become a node of the caller's graph, replayed long after the
+// registry has destroyed the event, and a query of another stream's probe may invalidate the
+// capture.  Such a launch does not run now, so it marks nothing either; the graph's replays never
+// pass through here and are invisible to the contamination check.
+bool stream_is_capturing(hipStream_t s);  // true also when the status is unknown
 uint64_t note_device_launch(int dev, hipStream_t s, int64_t bytes);
 uint64_t stream_last_launch(int dev, hipStream_t s);
 bool other_stream_may_run(int dev, hipStream_t s, uint64_t since);

@@ -241,6 +241,8 @@ bool MapPlanes::load(const PlanesShape &sh, bool accumulate, hipFunction_t *fn, 
             if (why) *why = f->second;
             return false;
         }
+        // thrown, not returned: a refusal is neither a remembered failure nor a reason to fall back
+        refuse_if_capturing("the generated k_map_planes kernel");
         Impl::Loaded n;
         bool deterministic = true;  // as ClayRtc::prepare: load errors are retried, compile errors not
         try {
