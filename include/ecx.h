@@ -189,6 +189,16 @@ int ecx_rs_encode_parity_blocked_batch(ecx_rs *rs, uint8_t *base, int64_t nstrip
 /* ecx_rs_decode_missing_batch over the blocked layout, in place (the same map). */
 int ecx_rs_decode_missing_blocked_batch(ecx_rs *rs, const uint8_t *shard_present, uint8_t *base, int64_t nstripes,
                                         int64_t byte_count, int64_t block_bytes, void *stream);
+/* ReedSolomon.isParityCorrect (ReedSolomon.java:129-178) over the blocked layout, read-only:
+ * verdict[s] (a device byte array of nstripes) is 1 exactly when
+ * isParityCorrect(shards of stripe s, 0, byte_count) holds on the stripe's natural shards, else
+ * 0.  block_bytes 0 = the recommended block.  One launch sets the verdicts, then the layout's two
+ * passes clear them: a mismatch in any block of a stripe, or in its tail, clears that stripe's
+ * byte.  Nothing is written to base.  nstripes == 0 touches nothing; byte_count == 0 makes every
+ * verdict 1.  Status codes as ecx_rs_is_parity_correct_batch; a negative block_bytes is
+ * ECX_E_ILLEGAL_ARGUMENT. */
+int ecx_rs_is_parity_correct_blocked_batch(ecx_rs *rs, const uint8_t *base, int64_t nstripes, int64_t byte_count,
+                                           int64_t block_bytes, uint8_t *verdict, void *stream);
 
 /* The same two blocked batches (encodeParity / decodeMissing, ReedSolomon.java:94-108, :189-286)
  * from HOST memory, in place (base: nstripes * n * byte_count bytes of
@@ -208,6 +218,22 @@ int ecx_rs_encode_parity_blocked_batch_host_devices(ecx_rs *rs, uint8_t *base, i
 int ecx_rs_decode_missing_blocked_batch_host_devices(ecx_rs *rs, const uint8_t *shard_present, uint8_t *base,
                                                      int64_t nstripes, int64_t byte_count, int64_t block_bytes,
                                                      const int *devices, int ndev);
+/* ReedSolomon.isParityCorrect (ReedSolomon.java:129-178) over HOST-memory stripes in the blocked
+ * layout (base: nstripes * n * byte_count bytes of pageable or pinned host memory, read-only;
+ * verdict: nstripes host bytes), as ecx_rs_is_parity_correct_blocked_batch: each of the layout's
+ * two passes is a pipelined host check (ecx_rs_is_parity_correct_batch_host) with one verdict
+ * byte per unit of the pass, folded per stripe on the host -- about 1 verdict byte per
+ * n * block_bytes data bytes.  Synchronous.  A store that keeps its stripes blocked scrubs them
+ * without an unpacking pass. */
+int ecx_rs_is_parity_correct_blocked_batch_host(ecx_rs *rs, const uint8_t *base, int64_t nstripes,
+                                                int64_t byte_count, int64_t block_bytes, uint8_t *verdict);
+/* ReedSolomon.isParityCorrect (ReedSolomon.java:129-178), the blocked host check over several
+ * GPUs of this process: each pass is split over the device entries as
+ * ecx_rs_is_parity_correct_batch_host_devices splits a check (the tails by byte ranges when
+ * there are fewer stripes than entries).  The device list is validated even for an empty batch. */
+int ecx_rs_is_parity_correct_blocked_batch_host_devices(ecx_rs *rs, const uint8_t *base, int64_t nstripes,
+                                                        int64_t byte_count, int64_t block_bytes, uint8_t *verdict,
+                                                        const int *devices, int ndev);
 
 /* As ecx_map_apply_batch, but XOR-accumulates: out ^= M * in. */
 int ecx_map_accumulate_batch(const ecx_map *map, const uint8_t *in, int64_t in_stripe_stride,

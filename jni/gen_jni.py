@@ -158,6 +158,7 @@ RULES = {
     "ecx_map_apply_batch_host_devices": ((), [NN("ndev"), A("devices", "ndev", err=ILL)]),
     "ecx_clay_perform_coding_batch_host_devices": ((), [NN("ndev"), A("devices", "ndev", err=ILL)]),
     "ecx_rs_is_parity_correct_batch_host_devices": ((), [NN("ndev"), A("devices", "ndev", err=ILL)]),
+    "ecx_rs_is_parity_correct_blocked_batch_host_devices": ((), [NN("ndev"), A("devices", "ndev", err=ILL)]),
     "ecx_rs_decode_missing_blocked_batch_host": (("rs",), [A("shard_present", RS_N)]),
     "ecx_rs_encode_parity_blocked_batch_host_devices": ((), [NN("ndev"), A("devices", "ndev", err=ILL)]),
     "ecx_rs_decode_missing_blocked_batch_host_devices": (("rs",), [A("shard_present", RS_N), NN("ndev"),
@@ -534,8 +535,10 @@ public final class EcxNative {
         jret = {"constchar*": "String", "int": "int", "void": "void"}[ret]
         cret = {"constchar*": "jstring", "int": "jint", "void": "void"}[ret]
         vis = "" if host_address_native(name) else "public "
-        if vis == "":
+        if vis == "" and name in BUFFER_VARIANTS:
             java.append("\n    /** Raw host addresses: package-private (use %sBuffer). */" % jname)
+        elif vis == "":
+            java.append("\n    /** Raw host addresses: package-private (no ByteBuffer form yet; INTEGRATION.md). */")
         java.append("\n    %sstatic native %s %s(%s);\n" % (vis, jret, jname, ", ".join(jparams)))
         body = []
         pre, copies, pin, unpin, post, args = [], [], [], [], [], []

@@ -781,6 +781,38 @@ class ReedSolomon:
                                                                 shard_stride, nstripes, firstByte, byteCount,
                                                                 _host_ptr(verdict), arr.ctypes.data, len(devs)))
 
+    def isParityCorrectBlockedBatch(self, base, nstripes, byteCount, verdict, blockBytes=0, stream=None) -> None:
+        """isParityCorrect over nstripes device-resident stripes in the blocked layout, read-only
+        (ecx_rs_is_parity_correct_blocked_batch; blockBytes 0 = the recommended block): the device
+        uint8 array ``verdict`` (nstripes bytes) receives 1 for each stripe whose natural shards
+        pass isParityCorrect over [0, byteCount), else 0.  Enqueued on ``stream``."""
+        _check_extent(base, nstripes * self.getTotalShardCount() * byteCount, "base")
+        _check_layout(verdict, 1, 0, 0, nstripes, 1, "verdict")
+        check(lib().ecx_rs_is_parity_correct_blocked_batch(self._h, _dev_ptr(base), nstripes, byteCount, blockBytes,
+                                                           _dev_ptr(verdict), _stream(stream)))
+
+    def isParityCorrectBlockedBatchHost(self, base, nstripes, byteCount, verdict, blockBytes=0) -> None:
+        """isParityCorrectBlockedBatch over HOST-memory stripes in the blocked layout
+        (ecx_rs_is_parity_correct_blocked_batch_host): the full blocks, then the tails, each a
+        pipelined host check; only verdict bytes come back, into the host uint8 array ``verdict``."""
+        _check_extent(base, nstripes * self.getTotalShardCount() * byteCount, "base")
+        _check_layout(verdict, 1, 0, 0, nstripes, 1, "verdict")
+        check(lib().ecx_rs_is_parity_correct_blocked_batch_host(self._h, _host_ptr(base), nstripes, byteCount,
+                                                                blockBytes, _host_ptr(verdict)))
+
+    def isParityCorrectBlockedBatchHostDevices(self, base, nstripes, byteCount, verdict, devices,
+                                               blockBytes=0) -> None:
+        """isParityCorrectBlockedBatchHost split over several GPUs of this process
+        (ecx_rs_is_parity_correct_blocked_batch_host_devices): each pass over contiguous ranges,
+        one worker thread and pipe per device entry."""
+        _check_extent(base, nstripes * self.getTotalShardCount() * byteCount, "base")
+        _check_layout(verdict, 1, 0, 0, nstripes, 1, "verdict")
+        devs = list(devices)
+        arr = np.ascontiguousarray(devs + [0], np.int32)  # never a null list: an empty one is ndev 0
+        check(lib().ecx_rs_is_parity_correct_blocked_batch_host_devices(self._h, _host_ptr(base), nstripes,
+                                                                        byteCount, blockBytes, _host_ptr(verdict),
+                                                                        arr.ctypes.data, len(devs)))
+
     def decodeMissingBatch(self, shards, shardPresent, stripe_stride, shard_stride, nstripes, offset, byteCount,
                            stream=None):
         """decodeMissing over nstripes device-resident stripes, in place (ecx_rs_decode_missing_batch)."""

@@ -114,6 +114,9 @@ SIGNATURES = {
     "ecx_rs_decode_map": (I, [P, P, ctypes.POINTER(P)]),
     "ecx_rs_encode_parity_batch": (I, [P, P, I64, I64, I64, I64, I64, P]),
     "ecx_rs_is_parity_correct_batch": (I, [P, P, I64, I64, I64, I64, I64, P, P]),
+    "ecx_rs_is_parity_correct_blocked_batch": (I, [P, P, I64, I64, I64, P, P]),
+    "ecx_rs_is_parity_correct_blocked_batch_host": (I, [P, P, I64, I64, I64, P]),
+    "ecx_rs_is_parity_correct_blocked_batch_host_devices": (I, [P, P, I64, I64, I64, P, P, I]),
     "ecx_rs_decode_missing_batch": (I, [P, P, P, I64, I64, I64, I64, I64, P]),
     "ecx_rs_decode_partial_batch": (I, [P, P, I, P, I64, P, I64, I64, I64, I64, I, P]),
     "ecx_rs_encode_partial_batch": (I, [P, I, P, I64, P, I64, I64, I64, I64, I, P]),

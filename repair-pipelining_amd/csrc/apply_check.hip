@@ -14,68 +14,40 @@
 // it shares with the previous chunk are checked twice -- harmless for a read-only check, and
 // it keeps every load a full 16-B access (byte counts that are multiples of 16 on aligned
 // layouts; otherwise a byte-safe launch covers the remainder).
+//
+// Over the blocked RS layout (blocked_layout.hpp) the same body runs as
+// k_gf_check_blocked: a launch's units are then the block rows of the layout's body pass, `full`
+// consecutive ones per caller stripe, and a mismatch clears the verdict of unit / full
+// (launch_check_blocked: the verdicts set once, then the body pass and the tail pass).
 #include "apply.hpp"
+#include "blocked_layout.hpp"
+#include "check_blocked.hpp"
 #include "layout_probe.hpp"  // note_device_launch
 
 namespace ecx {
 
+#define ECX_CHECK_BOUNDS(ROWS, DEPTH) (ROWS < kTileRows ? (DEPTH >= 16 ? 4 : 5) : (DEPTH >= 16 ? 3 : 5))
+
 template <bool SAFE, int DEPTH, int ROWS>
-__global__ void __launch_bounds__(kBlockThreads, ROWS < kTileRows ? (DEPTH >= 16 ? 4 : 5) : (DEPTH >= 16 ? 3 : 5)) k_gf_check(ApplyArgs a) {
-    const uint32_t w = logical_block(a.xcd_group, (uint32_t)a.n_tiles, (uint32_t)a.xcd_run);
-    const uint32_t tl = w % (uint32_t)a.n_tiles;
-    const uint32_t rest = w / (uint32_t)a.n_tiles;
-    const uint32_t nst = gridDim.x / ((uint32_t)a.n_tiles * (uint32_t)a.n_chunks);
-    int64_t s, c;
-    unit_of(rest, (uint32_t)a.n_chunks, nst, 0, (uint32_t)a.stagger, s, c);
-    s += a.stripe_begin;
-    c += a.chunk_begin;
-    int64_t cbase = c * kChunkBytes;
-    if (!SAFE && c == a.tail_chunk) cbase = a.nbytes - kChunkBytes;  // the shard's last full window
-    const uint32_t lane16 = threadIdx.x * 16;
-    int valid = 16;
-    if (SAFE) {
-        const int64_t v = a.nbytes - cbase - (int64_t)lane16;
-        valid = v <= 0 ? 0 : (v >= 16 ? 16 : (int)v);
-    }
-    cu32 *tile = plan_ptr(a.tiles) + __builtin_amdgcn_readfirstlane(tl) * kTileDwords;
-    const uint8_t *ib =
-        reinterpret_cast<const uint8_t *>(uniform64((uint64_t)(a.in + s * a.in_stripe_stride + cbase))) + lane16;
-    auto load = [&](uint32_t slot) -> u32x4 {  // padding entries read the zero page
-        const uint8_t *p = slot == kDummySlot ? a.zero_page + lane16 : ib + (int64_t)slot * a.in_slot_stride;
-        return SAFE ? load_partial(p, valid) : ld16<true>(p);
-    };
-    const int ecnt = (int)tile[1];  // padded to a multiple of DEPTH
-    const int nrows = (int)tile[2];
-    u32x4 acc[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) acc[r] = (u32x4){0u, 0u, 0u, 0u};
-    cu32 *ent = plan_ptr(a.entries) + (int64_t)tile[0] * kEntryDwords;
-    if (ecnt > 0) {
-        u32x4 ring[DEPTH];
-#pragma unroll
-        for (int u = 0; u < DEPTH; ++u) ring[u] = load(ent[u * kEntryDwords]);
-        const int last = ecnt - DEPTH;
-        for (int e0 = 0; e0 < last; e0 += DEPTH) {
-#pragma unroll
-            for (int u = 0; u < DEPTH; ++u) {
-                cu32 *r = ent + (int64_t)(e0 + u) * kEntryDwords;
-                apply_entry<false, ROWS>(r, ring[u], acc, nullptr);
-                ring[u] = load(r[DEPTH * kEntryDwords]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < DEPTH; ++u)
-            apply_entry<false, ROWS>(ent + (int64_t)(last + u) * kEntryDwords, ring[u], acc, nullptr);
-    }
-    uint32_t nz = 0;
-#pragma unroll
-    for (int o = 0; o < ROWS; ++o)
-        if (o < nrows) nz |= acc[o].x | acc[o].y | acc[o].z | acc[o].w;
-    // one vector byte store per wave that saw a mismatch (every writer stores the same 0)
-    if (__builtin_amdgcn_ballot_w64(nz != 0) && (threadIdx.x & 63) == 0) {
-        gu8 *v = (gu8 *)(a.out + s * a.out_stripe_stride);
-        *v = 0;
-    }
+__global__ void __launch_bounds__(kBlockThreads, ECX_CHECK_BOUNDS(ROWS, DEPTH)) k_gf_check(ApplyArgs a) {
+#define ECX_CHECK_VERDICT(s) (s)
+#include "apply_check_body.inc"
+#undef ECX_CHECK_VERDICT
+}
+
+// The check over one pass of a blocked batch (blocked_layout.hpp): the launch's units are block
+// rows, vd.divisor consecutive ones per caller stripe, and a mismatch clears the verdict of
+// unit / divisor instead of the unit's own.  a.out is the verdict of the launch's first unit's
+// stripe and vd.rem that unit's place in it.  The unit comes from the block index, so the quotient
+// is wave-uniform: two scalar multiplies (verdict_quot), and only in a workgroup that found a
+// mismatch.  A kernel of its own, not a field read by k_gf_check: the natural layout's
+// instantiations stay what they were.
+template <bool SAFE, int DEPTH, int ROWS>
+__global__ void __launch_bounds__(kBlockThreads, ECX_CHECK_BOUNDS(ROWS, DEPTH)) k_gf_check_blocked(ApplyArgs a, VerdictDiv vd) {
+#define ECX_CHECK_VERDICT(s) \
+    ((int64_t)verdict_quot(vd, __builtin_amdgcn_readfirstlane((uint32_t)((s) - a.stripe_begin))))
+#include "apply_check_body.inc"
+#undef ECX_CHECK_VERDICT
 }
 
 // verdict[s] = 1 for every stripe, ahead of the check's launches.  A kernel, not hipMemsetAsync:
@@ -90,7 +62,12 @@ __global__ void __launch_bounds__(256) k_set_verdicts(uint8_t *verdict, int64_t 
 
 namespace {
 template <bool SAFE, int D, int R>
-void launch_check_k(dim3 grid, hipStream_t stream, const ApplyArgs &a) {
+void launch_check_k(dim3 grid, hipStream_t stream, const ApplyArgs &a, const VerdictDiv *vd) {
+    if (vd) {
+        if (!SAFE) note_kernel("k_gf_check_blocked", SAFE, D, R);
+        hipLaunchKernelGGL((k_gf_check_blocked<SAFE, D, R>), grid, dim3(kBlockThreads), 0, stream, a, *vd);
+        return;
+    }
     if (!SAFE) note_kernel("k_gf_check", SAFE, D, R);
     hipLaunchKernelGGL((k_gf_check<SAFE, D, R>), grid, dim3(kBlockThreads), 0, stream, a);
 }
@@ -99,10 +76,11 @@ void launch_check_k(dim3 grid, hipStream_t stream, const ApplyArgs &a) {
 namespace {
 int check_depth(const Tuning &tu) { return tu.depth == 8 || tu.depth == 20 ? tu.depth : 4; }
 
-// Clears verdict[s] when a syndrome byte of stripe s over bytes [0, nbytes) is non-zero (the
-// verdicts were set to 1 by launch_check).
+// Clears verdict[s / divisor] when a syndrome byte of stripe s over bytes [0, nbytes) is non-zero
+// (the verdicts were set to 1 by launch_check / launch_check_blocked).  divisor 1: the natural
+// layout, k_gf_check; above 1 the stripes are the units of a blocked pass, k_gf_check_blocked.
 void launch_check_core(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_stride, int64_t in_slot_stride,
-                       uint8_t *verdict, int64_t nstripes, int64_t nbytes, hipStream_t stream) {
+                       uint8_t *verdict, int64_t nstripes, int64_t nbytes, hipStream_t stream, int64_t divisor = 1) {
     // Ring depth 4 (forced 8 / 20 with ecx_tune "depth"): on RS(17,3) 200,000-B shards depth 4 reads
     // 0.83 of HBM, depth 8 and 20 0.80 -- the short ring leaves registers for more resident waves
     // (profiles/r05_check_sweep.jsonl).  Accumulator rows: 4 when every tile has at most 4 (RS with
@@ -146,17 +124,22 @@ void launch_check_core(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_str
         for (int64_t s0 = 0; s0 < nstripes; s0 += stripes_per_launch) {
             a.stripe_begin = s0;
             const dim3 grid((unsigned)(std::min(stripes_per_launch, nstripes - s0) * per_stripe));
+            // blocked: the launch's verdicts start at its first unit's stripe, s0 / divisor, and
+            // the kernel divides (s0 % divisor + the unit's index in the launch)
+            const VerdictDiv vdiv = divisor > 1 ? verdict_div(divisor, s0) : VerdictDiv{};
+            const VerdictDiv *vd = divisor > 1 ? &vdiv : nullptr;
+            a.out = divisor > 1 ? verdict + s0 / divisor : verdict;
             if (safe) {
-                if (rows == 4) launch_check_k<true, 4, 4>(grid, stream, a);
-                else launch_check_k<true, 4, kTileRows>(grid, stream, a);
+                if (rows == 4) launch_check_k<true, 4, 4>(grid, stream, a, vd);
+                else launch_check_k<true, 4, kTileRows>(grid, stream, a, vd);
             } else if (rows == 4) {
-                if (depth == 20) launch_check_k<false, 20, 4>(grid, stream, a);
-                else if (depth == 8) launch_check_k<false, 8, 4>(grid, stream, a);
-                else launch_check_k<false, 4, 4>(grid, stream, a);
+                if (depth == 20) launch_check_k<false, 20, 4>(grid, stream, a, vd);
+                else if (depth == 8) launch_check_k<false, 8, 4>(grid, stream, a, vd);
+                else launch_check_k<false, 4, 4>(grid, stream, a, vd);
             } else {
-                if (depth == 20) launch_check_k<false, 20, kTileRows>(grid, stream, a);
-                else if (depth == 8) launch_check_k<false, 8, kTileRows>(grid, stream, a);
-                else launch_check_k<false, 4, kTileRows>(grid, stream, a);
+                if (depth == 20) launch_check_k<false, 20, kTileRows>(grid, stream, a, vd);
+                else if (depth == 8) launch_check_k<false, 8, kTileRows>(grid, stream, a, vd);
+                else launch_check_k<false, 4, kTileRows>(grid, stream, a, vd);
             }
         }
     };
@@ -204,6 +187,41 @@ void launch_check(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_stride, 
     int dev = 0;
     check_hip(hipGetDevice(&dev), "hipGetDevice");
     note_device_launch(dev, stream, nstripes * nbytes * cm.map().n_in);
+}
+
+// launch_check over a blocked batch (blocked_layout.hpp): verdict[s] for the nstripes caller
+// stripes, from the two passes of the layout.  One k_set_verdicts, then the body pass -- whose
+// units are block rows, `full` of them per stripe, so a mismatch clears verdict[unit / full] --
+// and the tail pass, one unit per stripe.  Both only ever clear, so a stripe passes when it
+// passes in every block and in its tail.  Each pass takes launch_check_core's alignment rules by
+// itself: recommended blocks are whole 4 KiB chunks; a tail slot shorter than a chunk has no
+// earlier bytes of its own shard before it (the shifted window would read the neighbouring
+// slot), so it runs byte-safe, as does every pass of an odd explicit block.
+void launch_check_blocked(CompiledMap &cm, const uint8_t *base, int n, int64_t nstripes, int64_t byte_count,
+                          int64_t block, uint8_t *verdict, hipStream_t stream) {
+    if (nstripes <= 0) return;
+    const LaunchStreamScope scope(stream);  // first use of device state is refused under capture (engine.hpp)
+    BlockedPlan plan;
+    const bool work = byte_count > 0 && cm.map().n_out != 0;
+    if (work) {
+        if (!blocked_plan(n, nstripes, byte_count, block, &plan))
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "blocked batch extent overflows");
+        // resident before anything is enqueued, as in launch_check
+        (void)cm.plan_for_current_device(check_depth(tuning()));
+        (void)cm.plan_for_current_device(4);
+        (void)zero_page_for_current_device();
+    }
+    hipLaunchKernelGGL(k_set_verdicts, dim3((unsigned)((nstripes + 255) / 256)), dim3(256), 0, stream, verdict, nstripes);
+    check_hip(hipGetLastError(), "k_set_verdicts launch");
+    for (int i = 0; i < plan.count; ++i) {
+        const BlockedPass &p = plan.pass[i];
+        launch_check_core(cm, base + p.offset, p.stripe_stride, p.slot_bytes, verdict, p.units, p.slot_bytes, stream,
+                          p.divisor);
+    }
+    if (plan.count == 0) return;
+    int dev = 0;
+    check_hip(hipGetDevice(&dev), "hipGetDevice");
+    note_device_launch(dev, stream, nstripes * byte_count * cm.map().n_in);
 }
 
 }  // namespace ecx

@@ -14,6 +14,8 @@
 #include <string>
 #include <tuple>
 
+#include "blocked_layout.hpp"
+#include "check_blocked.hpp"
 #include "clay_rtc.hpp"
 #include "map_rtc.hpp"
 #include "engine.hpp"
@@ -571,18 +573,18 @@ int64_t recommended_pitch(int64_t byte_count) {
     return c * kStep;
 }
 
-// The blocked layout's block: the largest power of two with n blocks
-// (one per shard of a stripe) within 1 MiB, 4 KiB..1 MiB -- 32 KiB for RS(17,3) (0.76 of HBM),
-// 64 KiB for RS(12,4) (0.816); one block of byte_count bytes for smaller shards.
-int64_t recommended_block(int n, int64_t byte_count) {
-    int64_t b = 1 << 20;
-    while (b > (4 << 10) && b * n > (1 << 20)) b >>= 1;
-    return byte_count >= b ? b : byte_count;
+// The blocked layout's block and its passes are blocked_layout.hpp's (no HIP header there: the
+// plan is tested on the CPU); here its refusals become status codes.
+int64_t resolve_block(int n, int64_t byte_count, int64_t block_bytes) {
+    int64_t block = 0;
+    if (!ecx::resolve_block(n, byte_count, block_bytes, &block))
+        throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative block size");
+    return block;
 }
 
-int64_t resolve_block(int n, int64_t byte_count, int64_t block_bytes) {
-    if (block_bytes < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative block size");
-    return block_bytes == 0 ? recommended_block(n, byte_count) : block_bytes;
+void blocked_plan_or_throw(int n, int64_t nstripes, int64_t byte_count, int64_t block, BlockedPlan *plan) {
+    if (!blocked_plan(n, nstripes, byte_count, block, plan))
+        throw Error(ECX_E_ILLEGAL_ARGUMENT, "blocked batch extent overflows");
 }
 
 // The two passes of a blocked batch (ecx.h), each in place: the full blocks as nstripes * full
@@ -591,14 +593,10 @@ int64_t resolve_block(int n, int64_t byte_count, int64_t block_bytes) {
 // (a std::function: this file's helpers sit inside the extern "C" block, where templates cannot)
 void blocked_passes(int n, int64_t nstripes, int64_t byte_count, int64_t block,
                     const std::function<void(int64_t, int64_t, int64_t, int64_t)> &pass) {
-    if (nstripes == 0 || byte_count == 0) return;
-    const int64_t full = byte_count / block, tail = byte_count % block;
-    int64_t stride = 0, units = 0, body = 0;
-    if (__builtin_mul_overflow((int64_t)n, block, &stride) || __builtin_mul_overflow(nstripes, full, &units) ||
-        __builtin_mul_overflow(units, stride, &body))
-        throw Error(ECX_E_ILLEGAL_ARGUMENT, "blocked batch extent overflows");
-    if (full > 0) pass((int64_t)0, stride, block, units);
-    if (tail > 0) pass(body, (int64_t)n * tail, tail, nstripes);
+    BlockedPlan plan;
+    blocked_plan_or_throw(n, nstripes, byte_count, block, &plan);
+    for (int i = 0; i < plan.count; ++i)
+        pass(plan.pass[i].offset, plan.pass[i].stripe_stride, plan.pass[i].slot_bytes, plan.pass[i].units);
 }
 
 void launch_blocked(CompiledMap &cm, uint8_t *base, int n, int64_t nstripes, int64_t byte_count, int64_t block,
@@ -1368,6 +1366,81 @@ int ecx_rs_is_parity_correct_batch_host_devices(ecx_rs *rs, const uint8_t *base,
                                                 int ndev) {
     return rs_check_host(__func__, rs, base, stripe_stride, shard_stride, nstripes, offset, byte_count, verdict,
                          devices, ndev, true);
+}
+
+int ecx_rs_is_parity_correct_blocked_batch(ecx_rs *rs, const uint8_t *base, int64_t nstripes, int64_t byte_count,
+                                           int64_t block_bytes, uint8_t *verdict, void *stream) {
+    return guarded(__func__, [&]() -> int {
+        if (!rs) throw Error(ECX_E_NULL, "null codec");
+        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        const int64_t block = resolve_block(rs->code.n(), byte_count, block_bytes);
+        if (nstripes == 0) return ECX_OK;
+        if (!base || !verdict) throw Error(ECX_E_NULL, "null device pointer");
+        launch_check_blocked(rs_check_map(rs)->cm, base, rs->code.n(), nstripes, byte_count, block, verdict,
+                             (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+
+namespace {
+// The blocked check from host memory: each pass of the layout is a pipelined host check
+// (host_pipe.cpp) with one verdict byte per unit of the pass; the body pass's go to a temporary
+// (1 byte per n * block data bytes) and are folded per stripe here, then ANDed with the tail
+// pass's.  With a device list each pass is split over the entries like any host check: the body
+// units by ranges, the tails by stripes (by byte ranges where there are fewer stripes than entries).
+int rs_check_blocked_host(const char *fn, ecx_rs *rs, const uint8_t *base, int64_t nstripes, int64_t byte_count,
+                          int64_t block_bytes, uint8_t *verdict, const int *devices, int ndev, bool multi) {
+    return guarded(fn, [&]() -> int {
+        if (!rs) throw Error(ECX_E_NULL, "null codec");
+        if (multi && !devices) throw Error(ECX_E_NULL, "null device list");
+        if (multi && ndev <= 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "empty device list");
+        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        const int n = rs->code.n();
+        const int64_t block = resolve_block(n, byte_count, block_bytes);
+        if (nstripes > 0 && (!base || !verdict)) throw Error(ECX_E_NULL, "null host pointer");
+        BlockedPlan plan;
+        blocked_plan_or_throw(n, nstripes, byte_count, block, &plan);
+        if (multi) for_device_ranges(devices, ndev, 0, [](int64_t, int64_t) {});  // the list, even for an empty batch
+        if (nstripes == 0) return ECX_OK;
+        CompiledMap &cm = rs_check_map(rs)->cm;
+        auto check = [&](const BlockedPass &p, uint8_t *v) {
+            if (multi) run_host_check_batch_devices(cm, base + p.offset, p.stripe_stride, p.slot_bytes, p.units,
+                                                    p.slot_bytes, v, devices, ndev);
+            else run_host_check_batch(cm, base + p.offset, p.stripe_stride, p.slot_bytes, p.units, p.slot_bytes, v);
+        };
+        if (plan.count == 0) {  // no bytes: every stripe passes, through the natural check's own path
+            check(BlockedPass{0, 0, 0, nstripes, 1}, verdict);
+            return ECX_OK;
+        }
+        std::vector<uint8_t> unit;
+        for (int i = 0; i < plan.count; ++i) {
+            const BlockedPass &p = plan.pass[i];
+            if (i == 0 && p.divisor == 1) {  // one unit per stripe: straight into the caller's array
+                check(p, verdict);
+                continue;
+            }
+            unit.assign((size_t)p.units, 0);
+            check(p, unit.data());
+            for (int64_t s = 0; s < nstripes; ++s) {
+                uint8_t ok = i == 0 ? 1 : verdict[s];
+                for (int64_t j = 0; j < p.divisor; ++j) ok = (uint8_t)(ok && unit[(size_t)(s * p.divisor + j)]);
+                verdict[s] = ok;
+            }
+        }
+        return ECX_OK;
+    });
+}
+}  // namespace
+
+int ecx_rs_is_parity_correct_blocked_batch_host(ecx_rs *rs, const uint8_t *base, int64_t nstripes,
+                                                int64_t byte_count, int64_t block_bytes, uint8_t *verdict) {
+    return rs_check_blocked_host(__func__, rs, base, nstripes, byte_count, block_bytes, verdict, nullptr, 0, false);
+}
+
+int ecx_rs_is_parity_correct_blocked_batch_host_devices(ecx_rs *rs, const uint8_t *base, int64_t nstripes,
+                                                        int64_t byte_count, int64_t block_bytes, uint8_t *verdict,
+                                                        const int *devices, int ndev) {
+    return rs_check_blocked_host(__func__, rs, base, nstripes, byte_count, block_bytes, verdict, devices, ndev, true);
 }
 
 int ecx_host_alloc(int64_t nbytes, void **out) {
