@@ -163,6 +163,37 @@ int ecx_rs_decode_missing_batch(ecx_rs *rs, const uint8_t *shard_present, uint8_
                                 int64_t shard_stride, int64_t nstripes, int64_t offset, int64_t byte_count,
                                 void *stream);
 
+/* A pattern set: erasure patterns of one codec compiled into one device plan, so that one launch
+ * decodes a batch whose stripes miss different shards -- the reference's decodeMissing takes
+ * shardPresent per call, i.e. per stripe (ReedSolomon.java:189-286).  The set holds a reference
+ * on its codec; it must outlive the work enqueued with it; the first batch call with it on a
+ * device uploads the plan and must be made outside stream capture. */
+typedef struct ecx_rs_pattern_set ecx_rs_pattern_set;
+/* decodeMissing's shardPresent (ReedSolomon.java:189-286) for each pattern of the set.
+ * patterns: npatterns x n host flags (1 = present), 1 <= npatterns <= 256; duplicates are
+ * allowed.  A pattern with fewer than k present: ECX_E_NOT_ENOUGH_SHARDS; one that misses more
+ * than 8 shards: ECX_E_ILLEGAL_ARGUMENT (decode such stripes with ecx_rs_decode_missing_batch). */
+int ecx_rs_pattern_set_create(ecx_rs *rs, const uint8_t *patterns, int npatterns, ecx_rs_pattern_set **out);
+/* Frees the set and its device plans, and drops its codec reference (ReedSolomon.java:189-286
+ * keeps no such state: this is the engine's). */
+void ecx_rs_pattern_set_destroy(ecx_rs_pattern_set *set);
+/* The set's pattern count, its codec's shard count n, and the largest number of shards a
+ * pattern misses (the rows decodeMissing rebuilds, ReedSolomon.java:189-286); each may be NULL. */
+int ecx_rs_pattern_set_info(const ecx_rs_pattern_set *set, int *npatterns, int *shards, int *max_missing);
+/* decodeMissing (ReedSolomon.java:189-286) per stripe, in place, layout of
+ * ecx_rs_decode_missing_batch: stripe s is decoded with pattern pattern_of_stripe[s] (a DEVICE
+ * byte array of nstripes); an id with no pattern (>= npatterns), or a pattern with nothing
+ * missing, leaves the stripe untouched.  Only enqueues. */
+int ecx_rs_decode_missing_batch_mixed(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                      uint8_t *base, int64_t stripe_stride, int64_t shard_stride,
+                                      int64_t nstripes, int64_t offset, int64_t byte_count, void *stream);
+/* Host helper for the shardPresent flags of many stripes (ReedSolomon.java:189-286): the
+ * distinct rows of present[nstripes][shards] in order of first appearance -> patterns (room for
+ * cap rows, 1 <= cap <= 256), their count, and ids[nstripes].  Flags compare as zero / non-zero
+ * and are written as 0 / 1.  More distinct rows than cap: ECX_E_ILLEGAL_ARGUMENT. */
+int ecx_rs_index_patterns(int shards, const uint8_t *present, int64_t nstripes, uint8_t *patterns, int cap,
+                          int *npatterns, uint8_t *ids);
+
 /* The engine's layout contract for RS batches in HBM (the reference
  * keeps every shard in its own byte[], ReedSolomonBenchmark.java:198, so the device layout
  * is the caller's choice).  BLOCKED layout of nstripes stripes of n = k + m shards of

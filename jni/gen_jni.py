@@ -8,7 +8,7 @@ export's parameters (the checks in tests/test_jni.py parse both files).  Java-si
 types:
 
   int / int64_t / uint64_t          int / long / long
-  handle (ecx_rs*, ecx_clay*, ecx_map*), void* stream / host or device address
+  handle (ecx_rs*, ecx_clay*, ecx_map*, ecx_rs_pattern_set*), void* stream / host or device address
                                     long
   ecx_X **out, void **out           long[] (element 0 receives the handle / address)
   host byte buffer (uint8_t *)      byte[] (pinned with GetPrimitiveArrayCritical; may be null
@@ -54,7 +54,7 @@ HEADER = ROOT / "include" / "ecx.h"
 OUT_C = ROOT / "jni" / "ecx_jni.c"
 OUT_JAVA = ROOT / "jni" / "com" / "backblaze" / "erasure" / "ecx" / "EcxNative.java"
 JCLASS = "com_backblaze_erasure_ecx_EcxNative"
-HANDLES = ("ecx_rs", "ecx_clay", "ecx_map")
+HANDLES = ("ecx_rs", "ecx_clay", "ecx_map", "ecx_rs_pattern_set")
 # byte pointers of these functions may be NULL (C side: "NULL = ..." or unused)
 NULLABLE = {("ecx_check_some_shards", "temp_buffer"), ("ecx_rs_is_parity_correct", "temp_buffer"),
             ("ecx_lrc_map", "block_present"), ("ecx_map_create", "in_slot"), ("ecx_map_create", "out_slot"),
@@ -64,6 +64,8 @@ NULLABLE = {("ecx_check_some_shards", "temp_buffer"), ("ecx_rs_is_parity_correct
             ("ecx_clay_geometry", "q"), ("ecx_clay_geometry", "t"), ("ecx_clay_geometry", "alpha"),
             ("ecx_clay_shape", "nodes"), ("ecx_clay_shape", "n_erased"), ("ecx_clay_shape", "alpha"),
             ("ecx_rs_shape", "data_shards"), ("ecx_rs_shape", "parity_shards"),
+            ("ecx_rs_pattern_set_info", "npatterns"), ("ecx_rs_pattern_set_info", "shards"),
+            ("ecx_rs_pattern_set_info", "max_missing"),
             ("ecx_gf_tables", "log_table"), ("ecx_gf_tables", "exp_table"), ("ecx_gf_tables", "mul_table")}
 
 ILL, IDX = "ECX_E_ILLEGAL_ARGUMENT", "ECX_E_INDEX"
@@ -133,6 +135,14 @@ RULES = {
     "ecx_map_slot_extent": ((), [A("max_in_slot", "1"), A("max_out_slot", "1")]),
     "ecx_rs_decode_map": (("rs",), [A("shard_present", RS_N)]),
     "ecx_rs_decode_missing_batch": (("rs",), [A("shard_present", RS_N)]),
+    # a pattern set: npatterns rows of n flags; its batch call takes device addresses only
+    # (pattern_of_stripe and base are longs, like every *_batch pointer)
+    "ecx_rs_pattern_set_create": (("rs",), [NN("npatterns"), A("patterns", "(int64_t)npatterns * (%s)" % RS_N)]),
+    "ecx_rs_pattern_set_info": ((), [A("npatterns", "1"), A("shards", "1"), A("max_missing", "1")]),
+    # the index helper: nstripes rows of `shards` flags in, up to cap rows and nstripes ids out
+    "ecx_rs_index_patterns": ((), [NN("shards", "nstripes", "cap"), A("present", "(int64_t)nstripes * shards"),
+                                   A("patterns", "(int64_t)cap * shards"), A("npatterns", "1"),
+                                   A("ids", "nstripes")]),
     "ecx_rs_blocked_layout": ((), [A("layout", "3")]),
     "ecx_rs_recommended_pitch": ((), [A("pitch", "1")]),
     "ecx_rs_decode_missing_blocked_batch": (("rs",), [A("shard_present", RS_N)]),

@@ -29,6 +29,7 @@ __all__ = [
     "lrc_encode", "lrc_encode_using_single", "lrc_decode", "sample_encode", "sample_decode",
     "device_count", "set_device", "fill_random", "count_mismatch", "shard_stripes",
     "ECChunk", "ECBlock", "ClayCodeHelper", "write_subchunk", "read_subchunk",
+    "PatternSet", "index_patterns",
 ]
 
 
@@ -824,6 +825,28 @@ class ReedSolomon:
         check(lib().ecx_rs_decode_missing_batch(self._h, pres.ctypes.data, _dev_ptr(shards), stripe_stride,
                                                 shard_stride, nstripes, offset, byteCount, _stream(stream)))
 
+    def patternSet(self, patterns) -> "PatternSet":
+        """The erasure patterns ``patterns`` ([npatterns][n] shardPresent flags, 1..256 rows) of
+        this code compiled into one device plan (ecx_rs_pattern_set_create), for
+        decodeMissingBatchMixed.  Close it once the work enqueued with it has finished."""
+        return PatternSet(self, patterns)
+
+    def decodeMissingBatchMixed(self, shards, patternSet, ids, stripe_stride, shard_stride, nstripes, offset,
+                                byteCount, stream=None):
+        """decodeMissing over nstripes device-resident stripes that miss different shards, in
+        place and in one launch (ecx_rs_decode_missing_batch_mixed): stripe s is decoded with
+        pattern ``ids[s]`` of ``patternSet``; ``ids`` is a device uint8 array of nstripes.  An id
+        without a pattern, or a pattern with nothing missing, leaves its stripe untouched."""
+        if patternSet._h is None:
+            raise EcxError(-6, "the pattern set is closed")
+        if patternSet.totalShardCount != self.getTotalShardCount():
+            raise EcxError(-1, "the pattern set belongs to another code")
+        _check_layout(shards, stripe_stride, shard_stride, self.getTotalShardCount() - 1, nstripes, offset + byteCount,
+                      "shards")
+        _check_layout(ids, 1, 0, 0, nstripes, 1, "ids")
+        check(lib().ecx_rs_decode_missing_batch_mixed(patternSet._h, _dev_ptr(ids), _dev_ptr(shards), stripe_stride,
+                                                      shard_stride, nstripes, offset, byteCount, _stream(stream)))
+
     def decodePartialBatch(self, shardPresent, shardIndex, inp, in_stripe_stride, acc, acc_stripe_stride,
                            acc_row_stride, nstripes, byteCount, isFirst, stream=None):
         """Batched decodeMissingSingle for every missing shard (data and parity)."""
@@ -853,6 +876,61 @@ class ReedSolomon:
         h = ctypes.c_void_p()
         check(lib().ecx_rs_decode_map(self._h, pres.ctypes.data, ctypes.byref(h)))
         return GfMap(h, owner=self)
+
+
+class PatternSet:
+    """ecx_rs_pattern_set: erasure patterns of one ReedSolomon code as one device plan
+    (ReedSolomon.patternSet).  It keeps its code alive; close() (idempotent) frees it."""
+
+    def __init__(self, rs: ReedSolomon, patterns):
+        pats = np.ascontiguousarray(np.asarray(patterns) != 0, dtype=np.uint8)
+        if pats.ndim != 2 or pats.shape[1] != rs.getTotalShardCount():
+            raise EcxError(-1, "patterns must be [npatterns][%d] shardPresent flags" % rs.getTotalShardCount())
+        h = ctypes.c_void_p()
+        self._h = None
+        check(lib().ecx_rs_pattern_set_create(rs._h, pats.ctypes.data, pats.shape[0], ctypes.byref(h)))
+        self._h = h
+        self._rs = rs
+        self.totalShardCount = rs.getTotalShardCount()
+
+    def info(self):
+        """(patterns, shards per stripe, most shards any pattern misses)."""
+        if self._h is None:
+            raise EcxError(-6, "the pattern set is closed")
+        v = [ctypes.c_int() for _ in range(3)]
+        check(lib().ecx_rs_pattern_set_info(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            lib().ecx_rs_pattern_set_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def index_patterns(present, cap: int = 256):
+    """(patterns, ids) of per-stripe shardPresent flags ``present`` ([nstripes][n]): the distinct
+    rows in order of first appearance (at most ``cap``), and for each stripe the index of its
+    row among them -- the inputs of ReedSolomon.patternSet and, once on the device, of
+    decodeMissingBatchMixed (ecx_rs_index_patterns)."""
+    pres = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
+    if pres.ndim != 2 or pres.shape[1] < 1:
+        raise EcxError(-1, "present must be [nstripes][n] flags")
+    nstripes, n = pres.shape
+    patterns = np.zeros((max(1, min(cap, 256)), n), np.uint8)
+    ids = np.zeros(max(1, nstripes), np.uint8)
+    count = ctypes.c_int()
+    check(lib().ecx_rs_index_patterns(n, pres.ctypes.data if nstripes else patterns.ctypes.data, nstripes,
+                                      patterns.ctypes.data, cap, ctypes.byref(count), ids.ctypes.data))
+    return patterns[:count.value].copy(), ids[:nstripes].copy()
 
 
 # ---------------------------------------------------------------- Clay

@@ -118,6 +118,11 @@ SIGNATURES = {
     "ecx_rs_is_parity_correct_blocked_batch_host": (I, [P, P, I64, I64, I64, P]),
     "ecx_rs_is_parity_correct_blocked_batch_host_devices": (I, [P, P, I64, I64, I64, P, P, I]),
     "ecx_rs_decode_missing_batch": (I, [P, P, P, I64, I64, I64, I64, I64, P]),
+    "ecx_rs_pattern_set_create": (I, [P, P, I, ctypes.POINTER(P)]),
+    "ecx_rs_pattern_set_destroy": (None, [P]),
+    "ecx_rs_pattern_set_info": (I, [P, PI, PI, PI]),
+    "ecx_rs_decode_missing_batch_mixed": (I, [P, P, P, I64, I64, I64, I64, I64, P]),
+    "ecx_rs_index_patterns": (I, [I, P, I64, P, I, PI, P]),
     "ecx_rs_decode_partial_batch": (I, [P, P, I, P, I64, P, I64, I64, I64, I64, I, P]),
     "ecx_rs_encode_partial_batch": (I, [P, I, P, I64, P, I64, I64, I64, I64, I, P]),
     "ecx_clay_create": (I, [I, I, P, I, ctypes.POINTER(P)]),

@@ -1,0 +1,114 @@
+// apply_mixed.hip -- k_gf_apply_mixed: ReedSolomon.decodeMissing (ReedSolomon.java:189-286) over
+// device-resident stripes that miss different shards, in one launch.
+//
+// A pattern set (mixed_plan.hpp, pattern_set.hpp) holds the decode maps of up to 256 erasure patterns
+// of one codec as one plan: the patterns' padded entry arrays back to back and 256 tile records.
+// One workgroup covers one (stripe, 4 KiB chunk), stripe-major.  It reads its stripe's pattern id
+// -- one byte of a device array the caller wrote -- makes it wave-uniform, and runs apply_tile
+// (apply.hpp) on record `id` exactly as k_gf_apply runs a single-tile map: the inner loop, the
+// load ring and the split-table arithmetic are the same code.  Every byte value names a record of
+// the plan (the unused ones have no rows), so there is no bounds branch: a stripe whose record has
+// no rows -- nothing missing, or an id without a pattern -- returns before it touches the shards.
+//
+// The id array is device memory written by an earlier kernel or copy of the caller's stream, so
+// it is read with an ordinary global load, not through the constant address space the plan uses.
+#include <algorithm>
+
+#include "apply.hpp"
+#include "layout_probe.hpp"  // note_device_launch
+#include "pattern_set.hpp"
+
+namespace ecx {
+
+template <bool SAFE, int DEPTH, int ROWS>
+__global__ void __launch_bounds__(kBlockThreads, ECX_APPLY_BOUNDS(ROWS, DEPTH)) k_gf_apply_mixed(ApplyArgs a,
+                                                                                                const uint8_t *ids) {
+    // (a launch covers whole stripes: gridDim.x = stripes x n_chunks)
+    const uint32_t nc = (uint32_t)a.n_chunks;
+    const int64_t s = (int64_t)(blockIdx.x / nc) + a.stripe_begin;
+    const int64_t c = (int64_t)(blockIdx.x % nc) + a.chunk_begin;
+    const uint32_t id = __builtin_amdgcn_readfirstlane((uint32_t)((const gu8 *)ids)[s]);
+    cu32 *tile = plan_ptr(a.tiles) + id * kTileDwords;
+    if (tile[2] == 0) return;  // wave-uniform: the whole workgroup leaves
+    const int64_t cbase = c * kChunkBytes;
+    int valid = 16;
+    if (SAFE) {
+        const int64_t v = a.nbytes - cbase - (int64_t)threadIdx.x * 16;
+        valid = v <= 0 ? 0 : (v >= 16 ? 16 : (int)v);
+    }
+    apply_tile<SAFE, true, SAFE ? 0 : 1, DEPTH, false, kBlockThreads, ROWS>(
+        a, tile, uniform64((uint64_t)(a.in + s * a.in_stripe_stride + cbase)),
+        uniform64((uint64_t)(a.out + s * a.out_stripe_stride + cbase)), threadIdx.x * 16, valid, nullptr);
+}
+
+namespace {
+template <bool SAFE, int D, int R>
+void launch_mixed_k(dim3 grid, hipStream_t stream, const ApplyArgs &a, const uint8_t *ids) {
+    if (!SAFE) note_kernel("k_gf_apply_mixed", SAFE, D, R);
+    hipLaunchKernelGGL((k_gf_apply_mixed<SAFE, D, R>), grid, dim3(kBlockThreads), 0, stream, a, ids);
+}
+}  // namespace
+
+// Instances: 4 or 8 accumulator rows (the set's largest pattern decides) at ring depth 4 or 8
+// for the full chunks of 16-B aligned layouts; one byte-safe instance (depth 4 -- every record of
+// either plan is padded to a multiple of 4 -- and 8 rows) for the partial last chunk and every
+// other layout.
+// There is no per-layout shape selection here: the work differs from stripe to stripe.
+void launch_apply_mixed(PatternSet &set, const uint8_t *ids, uint8_t *base, int64_t stripe_stride,
+                        int64_t slot_stride, int64_t nstripes, int64_t nbytes, hipStream_t stream) {
+    if (nstripes <= 0 || nbytes <= 0 || set.max_rows() == 0) return;
+    // the set's own ring depth, or the one ecx_tune "depth" forces (4 / 8; others have no instance)
+    const Tuning tu = tuning();
+    const int depth = tu.depth == 4 || tu.depth == 8 ? tu.depth : set.preferred_depth();
+    const MixedPlan &hp = set.plan(depth);
+    const LaunchStreamScope scope(stream);  // first use of device state is refused under capture (engine.hpp)
+    // resident before anything is enqueued: a first use refused on a capturing stream leaves no node behind
+    const MixedDevicePlan &plan = set.plan_for_current_device(depth);
+    const uint8_t *zero_page = zero_page_for_current_device();
+    const int rows = hp.max_rows <= 4 ? 4 : kTileRows;
+    // in place: the alignment conditions of a full-chunk launch are launch_rules' (BatchLayout)
+    const BatchLayout b{(uintptr_t)base, (uintptr_t)base, stripe_stride, slot_stride, stripe_stride,
+                        slot_stride,     nstripes,        nbytes,        false};
+    const int64_t full = b.aligned16() ? nbytes / kChunkBytes : 0;
+    const int64_t rest = (nbytes - full * kChunkBytes + kChunkBytes - 1) / kChunkBytes;
+    const int64_t max_blocks = (int64_t)1 << 30;
+    if (full + rest > max_blocks) throw Error(ECX_E_ILLEGAL_ARGUMENT, "byte_count is too large for one launch");
+
+    ApplyArgs a{};
+    a.in = base;
+    a.out = base;
+    a.entries = plan.entries;
+    a.tiles = plan.tiles;
+    a.zero_page = zero_page;
+    a.in_stripe_stride = a.out_stripe_stride = stripe_stride;
+    a.in_slot_stride = a.out_slot_stride = slot_stride;
+    a.nbytes = nbytes;
+    a.n_tiles = 1;
+    a.tail_chunk = -1;
+    auto run = [&](bool safe, int64_t chunk_begin, int64_t n_chunks) {
+        if (n_chunks <= 0) return;
+        a.chunk_begin = chunk_begin;
+        a.n_chunks = n_chunks;
+        const int64_t stripes_per_launch = std::max<int64_t>(1, max_blocks / n_chunks);
+        for (int64_t s0 = 0; s0 < nstripes; s0 += stripes_per_launch) {
+            a.stripe_begin = s0;
+            const dim3 grid((unsigned)(std::min(stripes_per_launch, nstripes - s0) * n_chunks));
+            if (safe) launch_mixed_k<true, 4, kTileRows>(grid, stream, a, ids);
+            else if (rows == 4 && depth == 8) launch_mixed_k<false, 8, 4>(grid, stream, a, ids);
+            else if (rows == 4) launch_mixed_k<false, 4, 4>(grid, stream, a, ids);
+            else if (depth == 8) launch_mixed_k<false, 8, kTileRows>(grid, stream, a, ids);
+            else launch_mixed_k<false, 4, kTileRows>(grid, stream, a, ids);
+        }
+    };
+    run(false, 0, full);
+    run(true, full, rest);
+    check_hip(hipGetLastError(), "k_gf_apply_mixed launch");
+    int dev = 0;
+    check_hip(hipGetDevice(&dev), "hipGetDevice");
+    // (input bytes, for the launch registry: as if every stripe read its longest pattern)
+    uint32_t inputs = 0;
+    for (int p = 0; p < hp.npatterns; ++p) inputs = std::max(inputs, hp.tiles[(size_t)p * kTileDwords + 3]);
+    note_device_launch(dev, stream, nstripes * nbytes * (int64_t)inputs);
+}
+
+}  // namespace ecx

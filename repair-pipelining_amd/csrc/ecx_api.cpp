@@ -21,6 +21,7 @@
 #include "engine.hpp"
 #include "host_pipe.hpp"
 #include "layout_probe.hpp"  // note_device_launch
+#include "pattern_set.hpp"
 
 using namespace ecx;
 
@@ -36,6 +37,14 @@ struct ecx_rs {
     std::mutex mu;
     std::unique_ptr<ecx_map> enc, check;
     std::map<std::string, std::unique_ptr<ecx_map>> dec, partial;  // plans live as long as the codec
+};
+
+// A pattern set (ecx.h): the decode maps of its patterns as one device plan.  `rs` is a reference
+// of the set's own on the codec whose maps it was built from.
+struct ecx_rs_pattern_set {
+    ecx_rs *rs = nullptr;
+    std::unique_ptr<PatternSet> set;
+    int npatterns = 0, max_missing = 0;
 };
 
 struct ecx_clay {
@@ -349,7 +358,7 @@ const char *ecx_status_string(int s) {
 }
 
 const char *ecx_last_error(void) { return g_last_error.c_str(); }
-int ecx_version(void) { return 106; }  // 1.06: round-5 ABI (check batches device and host, multi-GPU host batches, per-call executor)
+int ecx_version(void) { return 107; }  // 1.07: 1.06 (check batches device and host, multi-GPU host batches, per-call executor) + pattern sets
 
 // ---------------------------------------------------------------- device
 int ecx_device_count(int *count) {
@@ -557,6 +566,100 @@ int ecx_rs_decode_missing_batch(ecx_rs *rs, const uint8_t *shard_present, uint8_
         if (m->cm.map().n_out == 0) return ECX_OK;  // all present (ReedSolomon.java:216-218)
         launch_apply(const_cast<ecx_map *>(m)->cm, base + offset, stripe_stride, shard_stride, base + offset,
                      stripe_stride, shard_stride, nstripes, byte_count, (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+
+int ecx_rs_pattern_set_create(ecx_rs *rs, const uint8_t *patterns, int npatterns, ecx_rs_pattern_set **out) {
+    return guarded(__func__, [&]() -> int {
+        if (out) *out = nullptr;
+        if (!rs) throw Error(ECX_E_NULL, "null codec");
+        if (!patterns || !out) throw Error(ECX_E_NULL, "null pattern list or out pointer");
+        if (npatterns < 1 || npatterns > kMixedRecords)
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "a pattern set holds 1..256 patterns: " + std::to_string(npatterns));
+        const int n = rs->code.n(), k = rs->code.k(), m = rs->code.m();
+        int max_missing = 0;
+        for (int p = 0; p < npatterns; ++p) {
+            int np = 0;
+            for (int i = 0; i < n; ++i) np += patterns[(size_t)p * n + i] != 0;
+            if (np < k) throw Error(ECX_E_NOT_ENOUGH_SHARDS, "Not enough shards present (pattern " + std::to_string(p) + ")");
+            if (n - np > kTileRows)
+                throw Error(ECX_E_ILLEGAL_ARGUMENT,
+                            "pattern " + std::to_string(p) + " misses " + std::to_string(n - np) + " shards, a pattern set "
+                            "takes at most " + std::to_string(kTileRows) + ": decode such stripes with "
+                            "ecx_rs_decode_missing_batch, one pattern per call");
+            max_missing = std::max(max_missing, n - np);
+        }
+        // the set's own reference: equal codecs are one object, so its maps are the codec's
+        // (rs_decode_map: the first-k rule and parity-from-all-data stay the reference's)
+        ecx_rs *own = rs_registry().get(std::make_pair(k, m), [&] { return new ecx_rs(k, m); });
+        try {
+            std::vector<const CompiledMap *> maps;
+            for (int p = 0; p < npatterns; ++p)
+                maps.push_back(&rs_decode_map(own, present_vec(patterns + (size_t)p * n, n))->cm);
+            auto set = std::make_unique<ecx_rs_pattern_set>();
+            set->set = std::make_unique<PatternSet>(maps);
+            set->rs = own;
+            set->npatterns = npatterns;
+            set->max_missing = max_missing;
+            *out = set.release();
+        } catch (...) {
+            rs_registry().release(own);
+            throw;
+        }
+        return ECX_OK;
+    });
+}
+
+void ecx_rs_pattern_set_destroy(ecx_rs_pattern_set *set) {
+    if (!set) return;
+    ecx_rs *rs = set->rs;
+    delete set;  // the device plans first (hipFree), then the codec reference
+    rs_registry().release(rs);
+}
+
+int ecx_rs_pattern_set_info(const ecx_rs_pattern_set *set, int *npatterns, int *shards, int *max_missing) {
+    if (!set) return ECX_E_NULL;
+    if (npatterns) *npatterns = set->npatterns;
+    if (shards) *shards = set->rs->code.n();
+    if (max_missing) *max_missing = set->max_missing;
+    return ECX_OK;
+}
+
+int ecx_rs_decode_missing_batch_mixed(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                      uint8_t *base, int64_t stripe_stride, int64_t shard_stride,
+                                      int64_t nstripes, int64_t offset, int64_t byte_count, void *stream) {
+    return guarded(__func__, [&]() -> int {
+        if (!set) throw Error(ECX_E_NULL, "null pattern set");
+        if (nstripes < 0 || offset < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        if (!base || !pattern_of_stripe) throw Error(ECX_E_NULL, "null device pointer");
+        launch_apply_mixed(*set->set, pattern_of_stripe, base + offset, stripe_stride, shard_stride, nstripes,
+                           byte_count, (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+
+int ecx_rs_index_patterns(int shards, const uint8_t *present, int64_t nstripes, uint8_t *patterns, int cap,
+                          int *npatterns, uint8_t *ids) {
+    return guarded(__func__, [&]() -> int {
+        if (!present || !patterns || !npatterns || !ids) throw Error(ECX_E_NULL, "null array");
+        if (shards <= 0 || nstripes < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        if (cap < 1 || cap > kMixedRecords)
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "cap is outside 1..256: " + std::to_string(cap));
+        std::map<std::string, int> index;
+        std::string row((size_t)shards, '\0');
+        for (int64_t s = 0; s < nstripes; ++s) {
+            for (int i = 0; i < shards; ++i) row[(size_t)i] = present[(size_t)s * shards + i] ? 1 : 0;
+            auto it = index.find(row);
+            if (it == index.end()) {
+                if ((int)index.size() == cap)
+                    throw Error(ECX_E_ILLEGAL_ARGUMENT, "more than " + std::to_string(cap) + " distinct patterns");
+                std::memcpy(patterns + index.size() * (size_t)shards, row.data(), (size_t)shards);
+                it = index.emplace(row, (int)index.size()).first;
+            }
+            ids[s] = (uint8_t)it->second;
+        }
+        *npatterns = (int)index.size();
         return ECX_OK;
     });
 }

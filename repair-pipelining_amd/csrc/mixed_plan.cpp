@@ -1,0 +1,85 @@
+// mixed_plan.cpp -- the device plan of a pattern set and its host interpreter (mixed_plan.hpp).
+// Plain C++: built by the host compiler alone, like blocked_layout.cpp.
+#include "mixed_plan.hpp"
+
+#include <algorithm>
+
+namespace ecx {
+
+int mixed_depth(const MixedPatternIn *patterns, int npatterns) {
+    uint32_t min_count = 0xFFFFFFFFu;
+    for (int p = 0; p < npatterns; ++p) {
+        const uint32_t c = patterns[p].tile[1];
+        if (c > 0) min_count = std::min(min_count, c);
+    }
+    return min_count != 0xFFFFFFFFu && min_count >= 12 ? 8 : 4;
+}
+
+bool build_mixed_plan(const MixedPatternIn *patterns, int npatterns, int depth, MixedPlan *out) {
+    if (!patterns || !out || npatterns < 1 || npatterns > kMixedRecords || depth <= 0) return false;
+    for (int p = 0; p < npatterns; ++p) {
+        if (!patterns[p].tile || !patterns[p].entries) return false;
+        if (patterns[p].tile[2] > (uint32_t)kMixedTileRows) return false;
+    }
+    MixedPlan m;
+    m.npatterns = npatterns;
+    m.depth = depth;
+    m.tiles.assign((size_t)kMixedRecords * kMixedTileDwords, 0u);
+    for (int p = 0; p < npatterns; ++p) {
+        const uint32_t *src = patterns[p].tile;
+        uint32_t *tile = m.tiles.data() + (size_t)p * kMixedTileDwords;
+        const uint32_t begin = src[0], count = src[1];
+        std::copy(src, src + kMixedTileDwords, tile);
+        tile[0] = (uint32_t)(m.entries.size() / kMixedEntryDwords);
+        m.entries.insert(m.entries.end(), patterns[p].entries + (size_t)begin * kMixedEntryDwords,
+                         patterns[p].entries + (size_t)(begin + count) * kMixedEntryDwords);
+        const uint32_t padded = (count + (uint32_t)depth - 1) / (uint32_t)depth * (uint32_t)depth;
+        for (uint32_t d = count; d < padded; ++d) {
+            uint32_t rec[kMixedEntryDwords] = {0};
+            rec[0] = kMixedDummySlot;
+            m.entries.insert(m.entries.end(), rec, rec + kMixedEntryDwords);
+        }
+        tile[1] = padded;
+        m.max_rows = std::max(m.max_rows, (int)src[2]);
+    }
+    if (m.entries.empty()) m.entries.assign(kMixedEntryDwords, 0u);
+    *out = std::move(m);
+    return true;
+}
+
+bool emulate_mixed(const MixedPlan &p, uint8_t id, const uint8_t *in, uint8_t *out, int64_t len) {
+    auto table_byte = [](uint32_t lo, uint32_t hi, int idx) {
+        return (uint8_t)((idx < 4 ? lo : hi) >> (8 * (idx & 3)));
+    };
+    if (p.tiles.size() != (size_t)kMixedRecords * kMixedTileDwords || p.depth <= 0) return false;
+    const uint32_t *tile = p.tiles.data() + (size_t)id * kMixedTileDwords;
+    const uint32_t rows = tile[2];
+    if (rows == 0) return true;  // the kernel returns before it reads anything else
+    if (rows > (uint32_t)kMixedTileRows || tile[1] % (uint32_t)p.depth) return false;
+    if (((size_t)tile[0] + tile[1]) * kMixedEntryDwords > p.entries.size()) return false;
+    std::vector<uint8_t> acc((size_t)rows * len, 0);
+    for (uint32_t e = 0; e < tile[1]; ++e) {
+        const uint32_t *rec = p.entries.data() + ((size_t)tile[0] + e) * kMixedEntryDwords;
+        if (rec[0] == kMixedDummySlot) {
+            if (rec[1] | rec[2]) return false;
+            continue;  // reads the zero page: contributes nothing
+        }
+        const uint8_t *x = in + (int64_t)rec[0] * len;
+        for (uint32_t r = 0; r < rows; ++r) {
+            uint8_t *a = acc.data() + (size_t)r * len;
+            if (rec[2] & (1u << r))
+                for (int64_t i = 0; i < len; ++i) a[i] ^= x[i];
+            if (rec[1] & (1u << r)) {
+                const uint32_t *tb = rec + 4 + 5 * r;
+                for (int64_t i = 0; i < len; ++i)
+                    a[i] ^= table_byte(tb[0], tb[1], x[i] & 7) ^ table_byte(tb[2], tb[3], (x[i] >> 3) & 7) ^
+                            table_byte(tb[4], tb[4], x[i] >> 6);
+            }
+        }
+    }
+    for (uint32_t r = 0; r < rows; ++r)
+        std::copy(acc.begin() + (size_t)r * len, acc.begin() + (size_t)(r + 1) * len, out + (int64_t)tile[4 + r] * len);
+    return true;
+}
+
+}  // namespace ecx

@@ -1,0 +1,59 @@
+// pattern_set.cpp -- a pattern set's host plans and their per-device upload (pattern_set.hpp).
+#include "pattern_set.hpp"
+
+namespace ecx {
+
+PatternSet::PatternSet(const std::vector<const CompiledMap *> &maps) {
+    // each map's unpadded entries and tile record: its plan padded to a multiple of 1
+    std::vector<HostPlan> plans;
+    plans.reserve(maps.size());
+    std::vector<MixedPatternIn> in;
+    for (const CompiledMap *m : maps) {
+        if (m->n_tiles() > 1)
+            throw Error(ECX_E_ILLEGAL_ARGUMENT,
+                        "a pattern of a pattern set has more than " + std::to_string(kTileRows) + " rows");
+        plans.push_back(m->padded_plan(1));
+        in.push_back(MixedPatternIn{plans.back().entries.data(), plans.back().tiles.data()});
+    }
+    if (!build_mixed_plan(in.data(), (int)in.size(), 4, &plan4_) || !build_mixed_plan(in.data(), (int)in.size(), 8, &plan8_))
+        throw Error(ECX_E_ILLEGAL_ARGUMENT, "a pattern set holds 1.." + std::to_string(kMixedRecords) + " patterns");
+    preferred_depth_ = mixed_depth(in.data(), (int)in.size());
+}
+
+PatternSet::~PatternSet() {
+    for (auto &kv : dev_) {
+        int cur = 0;
+        if (hipGetDevice(&cur) != hipSuccess) continue;
+        (void)hipSetDevice(kv.first.first);
+        (void)hipFree(kv.second.entries);
+        (void)hipFree(kv.second.tiles);
+        (void)hipSetDevice(cur);
+    }
+}
+
+const MixedDevicePlan &PatternSet::plan_for_current_device(int depth) {
+    depth = depth == 8 ? 8 : 4;
+    const MixedPlan &hp = plan(depth);
+    int dev = 0;
+    check_hip(hipGetDevice(&dev), "hipGetDevice");
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = dev_.find({dev, depth});
+    if (it != dev_.end()) return it->second;
+    refuse_if_capturing("the pattern set's device plan");
+    MixedDevicePlan p;
+    auto upload = [](uint32_t **dst, const std::vector<uint32_t> &src, const char *what) {
+        check_hip(hipMalloc(dst, src.size() * 4), what);
+        check_hip(hipMemcpy(*dst, src.data(), src.size() * 4, hipMemcpyHostToDevice), "pattern set upload");
+    };
+    try {
+        upload(&p.entries, hp.entries, "hipMalloc(pattern set entries)");
+        upload(&p.tiles, hp.tiles, "hipMalloc(pattern set tiles)");
+    } catch (...) {  // a half-uploaded plan is never published
+        (void)hipFree(p.entries);
+        (void)hipFree(p.tiles);
+        throw;
+    }
+    return dev_.emplace(std::make_pair(dev, depth), p).first->second;
+}
+
+}  // namespace ecx
