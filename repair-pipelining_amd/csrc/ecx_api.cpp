@@ -1,11 +1,12 @@
 // ecx_api.cpp -- the C ABI (include/ecx.h).  Translates planner/HIP errors into
 // ecx_status codes; every arithmetic entry point executes on the HIP device.
+// The exports get their C linkage from their declarations in ecx.h and ecx_tune.h: an entry point
+// defined here without one there is not exported under its name.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
-#include <functional>
 #include <list>
 #include <map>
 #include <memory>
@@ -22,6 +23,8 @@
 #include "host_pipe.hpp"
 #include "layout_probe.hpp"  // note_device_launch
 #include "pattern_set.hpp"
+#include "tune_table.hpp"
+#include "../../include/ecx_tune.h"
 
 using namespace ecx;
 
@@ -339,8 +342,6 @@ Registry<ecx_clay, std::tuple<int, int, int, std::vector<int>, int>> &clay_regis
     return r;
 }
 }  // namespace
-
-extern "C" {
 
 const char *ecx_status_string(int s) {
     switch (s) {
@@ -690,36 +691,55 @@ void blocked_plan_or_throw(int n, int64_t nstripes, int64_t byte_count, int64_t 
         throw Error(ECX_E_ILLEGAL_ARGUMENT, "blocked batch extent overflows");
 }
 
-// The two passes of a blocked batch (ecx.h), each in place: the full blocks as nstripes * full
-// "stripes" of n block-sized slots, then the tails as nstripes stripes of n tail-sized slots.
-// pass(offset, stripe_stride, slot_bytes, units) runs the map over one of them.
-// (a std::function: this file's helpers sit inside the extern "C" block, where templates cannot)
-void blocked_passes(int n, int64_t nstripes, int64_t byte_count, int64_t block,
-                    const std::function<void(int64_t, int64_t, int64_t, int64_t)> &pass) {
-    BlockedPlan plan;
-    blocked_plan_or_throw(n, nstripes, byte_count, block, &plan);
-    for (int i = 0; i < plan.count; ++i)
-        pass(plan.pass[i].offset, plan.pass[i].stripe_stride, plan.pass[i].slot_bytes, plan.pass[i].units);
-}
+// Where a blocked encode / decode batch runs: on a stream over device memory, or from host memory
+// as pipelined host batches (host_pipe.cpp), split over a device list where there is one.
+struct BlockedTarget {
+    bool host, multi;
+    void *stream;
+    const int *devices;
+    int ndev;
+};
 
-void launch_blocked(CompiledMap &cm, uint8_t *base, int n, int64_t nstripes, int64_t byte_count, int64_t block,
-                    hipStream_t stream) {
-    blocked_passes(n, nstripes, byte_count, block, [&](int64_t off, int64_t ss, int64_t len, int64_t units) {
-        launch_apply(cm, base + off, ss, len, base + off, ss, len, units, len, stream);
-    });
-}
-
-// The same two passes from host memory: two pipelined host batches (host_pipe.cpp), the second
-// after the first has drained (each is synchronous).  With a device list (ndev > 0) each pass is
-// split over the entries like any host batch: the full blocks as nstripes * full small stripes,
-// the tails by stripes (by byte ranges where there are fewer stripes than entries).
-void host_blocked(CompiledMap &cm, uint8_t *base, int n, int64_t nstripes, int64_t byte_count, int64_t block,
-                  const int *devices = nullptr, int ndev = 0) {
-    const bool multi = ndev != 0 || devices;
-    if (multi) for_device_ranges(devices, ndev, 0, [](int64_t, int64_t) {});  // the list, even for an empty batch
-    blocked_passes(n, nstripes, byte_count, block, [&](int64_t off, int64_t ss, int64_t len, int64_t units) {
-        if (multi) run_host_batch_devices(cm, base + off, ss, len, base + off, ss, len, units, len, devices, ndev);
-        else run_host_batch(cm, base + off, ss, len, base + off, ss, len, units, len);
+// The one body of the six blocked encode / decode exports (ecx.h); tests/test_blocked_apply_cpu.py
+// pins the order of its checks.  The two passes of the layout run in place: the full blocks as
+// nstripes * full "stripes" of n block-sized slots, then the tails as nstripes stripes of n
+// tail-sized slots.  From host memory each pass is a host batch of its own, the second after the
+// first has drained (each is synchronous); with a device list each is split over the entries like
+// any host batch: the full blocks as nstripes * full small stripes, the tails by stripes (by byte
+// ranges where there are fewer stripes than entries).
+int rs_apply_blocked(const char *fn, ecx_rs *rs, bool decode, const uint8_t *shard_present, uint8_t *base,
+                     int64_t nstripes, int64_t byte_count, int64_t block_bytes, const BlockedTarget &to) {
+    return guarded(fn, [&]() -> int {
+        if (to.host && !rs) throw Error(ECX_E_NULL, "null codec");  // (the device forms do not look)
+        if (to.multi && !to.devices) throw Error(ECX_E_NULL, "null device list");
+        if (to.multi && to.ndev <= 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "empty device list");
+        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        // a host batch of no stripes needs no buffer
+        if (!base && !to.host) throw Error(ECX_E_NULL, "null device pointer");
+        if (!base && nstripes > 0) throw Error(ECX_E_NULL, "null host pointer");
+        const ecx_map *m = nullptr;
+        const int st = decode ? ecx_rs_decode_map(rs, shard_present, &m)  // Not enough shards -> -2
+                              : ecx_rs_encode_map(rs, &m);
+        if (st) return st;
+        CompiledMap &cm = const_cast<ecx_map *>(m)->cm;
+        const int n = rs->code.n();
+        const int64_t block = resolve_block(n, byte_count, block_bytes);
+        if (decode && cm.map().n_out == 0) {  // all present (ReedSolomon.java:216-218): nothing to touch,
+            if (!to.multi) return ECX_OK;
+            nstripes = 0;  // but the device list is still checked
+        }
+        if (to.multi) for_device_ranges(to.devices, to.ndev, 0, [](int64_t, int64_t) {});  // even for an empty batch
+        BlockedPlan plan;
+        blocked_plan_or_throw(n, nstripes, byte_count, block, &plan);
+        for (int i = 0; i < plan.count; ++i) {
+            const BlockedPass &p = plan.pass[i];
+            uint8_t *at = base + p.offset;
+            const int64_t ss = p.stripe_stride, len = p.slot_bytes;
+            if (to.multi) run_host_batch_devices(cm, at, ss, len, at, ss, len, p.units, len, to.devices, to.ndev);
+            else if (to.host) run_host_batch(cm, at, ss, len, at, ss, len, p.units, len);
+            else launch_apply(cm, at, ss, len, at, ss, len, p.units, len, (hipStream_t)to.stream);
+        }
+        return ECX_OK;
     });
 }
 }  // namespace
@@ -749,101 +769,39 @@ int ecx_rs_recommended_pitch(int data_shards, int parity_shards, int64_t byte_co
 
 int ecx_rs_encode_parity_blocked_batch(ecx_rs *rs, uint8_t *base, int64_t nstripes, int64_t byte_count,
                                        int64_t block_bytes, void *stream) {
-    return guarded(__func__, [&]() -> int {
-        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
-        if (!base) throw Error(ECX_E_NULL, "null device pointer");
-        const ecx_map *m = nullptr;
-        const int st = ecx_rs_encode_map(rs, &m);
-        if (st) return st;
-        const int64_t block = resolve_block(rs->code.n(), byte_count, block_bytes);
-        launch_blocked(const_cast<ecx_map *>(m)->cm, base, rs->code.n(), nstripes, byte_count, block,
-                       (hipStream_t)stream);
-        return ECX_OK;
-    });
+    return rs_apply_blocked(__func__, rs, false, nullptr, base, nstripes, byte_count, block_bytes,
+                            {false, false, stream, nullptr, 0});
 }
 
 int ecx_rs_decode_missing_blocked_batch(ecx_rs *rs, const uint8_t *shard_present, uint8_t *base, int64_t nstripes,
                                         int64_t byte_count, int64_t block_bytes, void *stream) {
-    return guarded(__func__, [&]() -> int {
-        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
-        if (!base) throw Error(ECX_E_NULL, "null device pointer");
-        const ecx_map *m = nullptr;
-        const int st = ecx_rs_decode_map(rs, shard_present, &m);  // Not enough shards -> -2
-        if (st) return st;
-        const int64_t block = resolve_block(rs->code.n(), byte_count, block_bytes);
-        if (m->cm.map().n_out == 0) return ECX_OK;  // all present (ReedSolomon.java:216-218)
-        launch_blocked(const_cast<ecx_map *>(m)->cm, base, rs->code.n(), nstripes, byte_count, block,
-                       (hipStream_t)stream);
-        return ECX_OK;
-    });
+    return rs_apply_blocked(__func__, rs, true, shard_present, base, nstripes, byte_count, block_bytes,
+                            {false, false, stream, nullptr, 0});
 }
 
 int ecx_rs_encode_parity_blocked_batch_host(ecx_rs *rs, uint8_t *base, int64_t nstripes, int64_t byte_count,
                                             int64_t block_bytes) {
-    return guarded(__func__, [&]() -> int {
-        if (!rs) throw Error(ECX_E_NULL, "null codec");
-        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
-        if (nstripes > 0 && !base) throw Error(ECX_E_NULL, "null host pointer");
-        const ecx_map *m = nullptr;
-        const int st = ecx_rs_encode_map(rs, &m);
-        if (st) return st;
-        const int64_t block = resolve_block(rs->code.n(), byte_count, block_bytes);
-        host_blocked(const_cast<ecx_map *>(m)->cm, base, rs->code.n(), nstripes, byte_count, block);
-        return ECX_OK;
-    });
+    return rs_apply_blocked(__func__, rs, false, nullptr, base, nstripes, byte_count, block_bytes,
+                            {true, false, nullptr, nullptr, 0});
 }
 
 int ecx_rs_decode_missing_blocked_batch_host(ecx_rs *rs, const uint8_t *shard_present, uint8_t *base,
                                              int64_t nstripes, int64_t byte_count, int64_t block_bytes) {
-    return guarded(__func__, [&]() -> int {
-        if (!rs) throw Error(ECX_E_NULL, "null codec");
-        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
-        if (nstripes > 0 && !base) throw Error(ECX_E_NULL, "null host pointer");
-        const ecx_map *m = nullptr;
-        const int st = ecx_rs_decode_map(rs, shard_present, &m);  // Not enough shards -> -2
-        if (st) return st;
-        const int64_t block = resolve_block(rs->code.n(), byte_count, block_bytes);
-        if (m->cm.map().n_out == 0) return ECX_OK;  // all present (ReedSolomon.java:216-218)
-        host_blocked(const_cast<ecx_map *>(m)->cm, base, rs->code.n(), nstripes, byte_count, block);
-        return ECX_OK;
-    });
+    return rs_apply_blocked(__func__, rs, true, shard_present, base, nstripes, byte_count, block_bytes,
+                            {true, false, nullptr, nullptr, 0});
 }
 
 int ecx_rs_encode_parity_blocked_batch_host_devices(ecx_rs *rs, uint8_t *base, int64_t nstripes, int64_t byte_count,
                                                     int64_t block_bytes, const int *devices, int ndev) {
-    return guarded(__func__, [&]() -> int {
-        if (!rs) throw Error(ECX_E_NULL, "null codec");
-        if (!devices) throw Error(ECX_E_NULL, "null device list");
-        if (ndev <= 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "empty device list");
-        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
-        if (nstripes > 0 && !base) throw Error(ECX_E_NULL, "null host pointer");
-        const ecx_map *m = nullptr;
-        const int st = ecx_rs_encode_map(rs, &m);
-        if (st) return st;
-        const int64_t block = resolve_block(rs->code.n(), byte_count, block_bytes);
-        host_blocked(const_cast<ecx_map *>(m)->cm, base, rs->code.n(), nstripes, byte_count, block, devices, ndev);
-        return ECX_OK;
-    });
+    return rs_apply_blocked(__func__, rs, false, nullptr, base, nstripes, byte_count, block_bytes,
+                            {true, true, nullptr, devices, ndev});
 }
 
 int ecx_rs_decode_missing_blocked_batch_host_devices(ecx_rs *rs, const uint8_t *shard_present, uint8_t *base,
                                                      int64_t nstripes, int64_t byte_count, int64_t block_bytes,
                                                      const int *devices, int ndev) {
-    return guarded(__func__, [&]() -> int {
-        if (!rs) throw Error(ECX_E_NULL, "null codec");
-        if (!devices) throw Error(ECX_E_NULL, "null device list");
-        if (ndev <= 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "empty device list");
-        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
-        if (nstripes > 0 && !base) throw Error(ECX_E_NULL, "null host pointer");
-        const ecx_map *m = nullptr;
-        const int st = ecx_rs_decode_map(rs, shard_present, &m);  // Not enough shards -> -2
-        if (st) return st;
-        const int64_t block = resolve_block(rs->code.n(), byte_count, block_bytes);
-        // all present (ReedSolomon.java:216-218): nothing to touch, the device list still checked
-        host_blocked(const_cast<ecx_map *>(m)->cm, base, rs->code.n(), m->cm.map().n_out == 0 ? 0 : nstripes,
-                     byte_count, block, devices, ndev);
-        return ECX_OK;
-    });
+    return rs_apply_blocked(__func__, rs, true, shard_present, base, nstripes, byte_count, block_bytes,
+                            {true, true, nullptr, devices, ndev});
 }
 
 int ecx_rs_encode_parity(ecx_rs *rs, uint8_t *const *shards, int shard_count, int shard_length, int offset,
@@ -1581,224 +1539,31 @@ int ecx_host_unregister(void *ptr) {
 }
 
 // ---------------------------------------------------------------- tuning hook (include/ecx_tune.h)
+// The keys, their classes and their ranges are tune_table.cpp's rows; here only what the table
+// must not do itself: the environment, the tuning lock and the "roctx" atomic.
 namespace {
-bool diagnostic_builds_allowed() {
-    const char *v = std::getenv("ECX_DIAGNOSTIC");
+bool env_is_1(const char *name) {
+    const char *v = std::getenv(name);
     return v && std::strcmp(v, "1") == 0;
-}
-
-// Knobs of the measured-and-rejected kernels and builds: accepted by
-// the diagnostic library only (`make DIAG=1`, libecx_diag.so).
-bool lab_key(const std::string &k) {
-    return k == "bitslice" || k == "lds_lut" || k == "wave_groups" || k == "rtc_units" || k == "rtc_persist" ||
-           k == "rtc_diag" || k == "occ_lds" || k == "units";
-}
-
-// Deployment knobs (host pipeline, per-call plan cache, markers, the layout selection's on/off):
-// what a production caller may set.  Every other key changes a kernel's launch shape -- results
-// are identical, only speed differs -- and is accepted only by the diagnostic library or when the
-// process opted in with ECX_SHAPE_KNOBS=1 in its environment (read once, at the first ecx_tune), so
-// one library loaded into a JVM cannot reshape every other caller's launches.
-bool deployment_key(const std::string &k) {
-    return k == "host_chunk_kib" || k == "host_buffers" || k == "host_gather_kib" || k == "host_zero_copy" ||
-           k == "host_contexts" || k == "host_exec_kib" || k == "roctx" || k == "plan_cache" || k == "layout_select";
-}
-
-bool shape_knobs_enabled() {
-    static const bool on = [] {
-        const char *v = std::getenv("ECX_SHAPE_KNOBS");
-        return ECX_DIAG || (v && std::strcmp(v, "1") == 0);
-    }();
-    return on;
-}
-
-// One ecx_tune key, under the tuning lock.
-int set_tune(Tuning &t, const std::string &k, int value) {
-    if (!ECX_DIAG && lab_key(k)) return ECX_E_ILLEGAL_ARGUMENT;
-    if (!deployment_key(k) && !shape_knobs_enabled()) return ECX_E_ILLEGAL_ARGUMENT;
-    if (k == "depth") {
-        if (value != 0 && value != 2 && value != 4 && value != 8 && value != 10 && value != 12 && value != 16 &&
-            value != 20 && value != 24)
-            return ECX_E_ILLEGAL_ARGUMENT;
-        t.depth = value;
-    }
-    else if (k == "nontemporal") {
-        if (value < 0 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.nontemporal = value;
-    }
-    else if (k == "xcd_group") {
-        if (value < 0 || value > 3) return ECX_E_ILLEGAL_ARGUMENT;
-        t.xcd_group = value;
-    }
-    else if (k == "xcd_misaligned") {
-        if (value < 0 || value > 1) return ECX_E_ILLEGAL_ARGUMENT;
-        t.xcd_misaligned = value;
-    }
-    else if (k == "xcd_run") {
-        if (value < 1 || value > 4096) return ECX_E_ILLEGAL_ARGUMENT;
-        t.xcd_run = value;
-    }
-    else if (k == "wave_groups") {
-        if (value < 0 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.wave_groups = value;
-    }
-    else if (k == "store_scope") t.store_scope = value != 0;
-    else if (k == "occ_lds") {
-        if (value < -1 || value > 65536) return ECX_E_ILLEGAL_ARGUMENT;
-        t.occ_lds = value;
-    }
-    else if (k == "chunk_major") t.chunk_major = value != 0;
-    else if (k == "stagger") {
-        if (value < 0 || value > 64) return ECX_E_ILLEGAL_ARGUMENT;
-        t.stagger = value;
-    }
-    else if (k == "small_tiles") {
-        if (value < 0 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.small_tiles = value;
-    }
-    else if (k == "host_zero_copy") t.host_zero_copy = value != 0;
-    else if (k == "plan_cache") {
-        if (value < 0 || value > 4096) return ECX_E_ILLEGAL_ARGUMENT;
-        t.plan_cache = value;
-    }
-    else if (k == "skew_chunks") {
-        if (value < 0 || value > 4 || value == 3) return ECX_E_ILLEGAL_ARGUMENT;
-        t.skew_chunks = value;
-    }
-    else if (k == "layout_select") {
-        if (value < 0 || value > 1) return ECX_E_ILLEGAL_ARGUMENT;
-        t.layout_select = value;
-    }
-    else if (k == "wide_tiles") {
-        if (value < 0 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.wide_tiles = value;
-    }
-    else if (k == "block_threads") {
-        if (value != 0 && value != 64 && value != 256) return ECX_E_ILLEGAL_ARGUMENT;
-        t.block_threads = value;
-    }
-    else if (k == "lds_tables") {
-        if (value < 0 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.lds_tables = value;
-    }
-    else if (k == "host_chunk_kib") {
-        if (value < 1) return ECX_E_ILLEGAL_ARGUMENT;
-        t.host_chunk = (int64_t)value << 10;
-    }
-    else if (k == "host_gather_kib") {
-        if (value < 0) return ECX_E_ILLEGAL_ARGUMENT;
-        t.host_gather_max = (int64_t)value << 10;
-    }
-    else if (k == "clay_rtc") {
-        if (value < 0 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.clay_rtc = value;
-    }
-    else if (k == "rtc_lookahead") {
-        if (value < 0 || value > 31) return ECX_E_ILLEGAL_ARGUMENT;
-        // bit 4 is the DIAGNOSTIC movement-only build, whose outputs are not the repair:
-        // refused unless this is the diagnostic library and the process opted in with ECX_DIAGNOSTIC=1
-        if ((value & 16) && !(ECX_DIAG && diagnostic_builds_allowed())) return ECX_E_ILLEGAL_ARGUMENT;
-        t.rtc_lookahead = value;
-    }
-    else if (k == "rtc_xcd") {
-        if (value < 0 || value > 4) return ECX_E_ILLEGAL_ARGUMENT;
-        t.rtc_xcd = value;
-    }
-    else if (k == "rtc_group") t.rtc_group = value != 0;
-    else if (k == "rtc_diag") {
-        if (value < 0 || value > 31) return ECX_E_ILLEGAL_ARGUMENT;
-        if (value && !diagnostic_builds_allowed()) return ECX_E_ILLEGAL_ARGUMENT;  // outputs not the repair
-        t.rtc_diag = value;
-    }
-    else if (k == "rtc_sched") {
-        if (value < 0 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.rtc_sched = value;
-    }
-    else if (k == "rtc_wide") {
-        if (value < 0 || value > 1) return ECX_E_ILLEGAL_ARGUMENT;
-        t.rtc_wide = value;
-    }
-    else if (k == "rtc_nt") {
-        if (value < 0 || value > 15) return ECX_E_ILLEGAL_ARGUMENT;
-        t.rtc_nt = value;
-    }
-    else if (k == "rtc_units") {
-        if (value < 1 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.rtc_units = value;
-    }
-    else if (k == "rtc_persist") {
-        if (value < 0 || value > 8) return ECX_E_ILLEGAL_ARGUMENT;
-        t.rtc_persist = value;
-    }
-    else if (k == "rtc_waves") {
-        if (value < 2 || value > 4) return ECX_E_ILLEGAL_ARGUMENT;
-        t.rtc_waves = value;
-    }
-    else if (k == "map_planes") {
-        if (value < 0 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.map_planes = value;
-    }
-    else if (k == "planes_lookahead") {
-        if (value < 0 || value > 15) return ECX_E_ILLEGAL_ARGUMENT;
-        t.planes_lookahead = value;
-    }
-    else if (k == "planes_waves") {
-        if (value < 1 || value > 4) return ECX_E_ILLEGAL_ARGUMENT;
-        t.planes_waves = value;
-    }
-    else if (k == "bitslice") {
-        if (value < 0 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.bitslice = value;
-    }
-    else if (k == "host_contexts") {
-        if (value < 0 || value > 1) return ECX_E_ILLEGAL_ARGUMENT;
-        t.host_contexts = value;
-    }
-    else if (k == "roctx") {
-        if (value < 0 || value > 1) return ECX_E_ILLEGAL_ARGUMENT;
-        g_roctx.store(value);
-    }
-    else if (k == "lds_lut") {
-        if (value < 0 || value > 2) return ECX_E_ILLEGAL_ARGUMENT;
-        t.lds_lut = value;
-    }
-    else if (k == "units") {
-        if (value != 1 && value != 2 && value != 4) return ECX_E_ILLEGAL_ARGUMENT;
-        t.units = value;
-    }
-    else if (k == "host_exec_kib") {
-        if (value < 0 || value > (1 << 20)) return ECX_E_ILLEGAL_ARGUMENT;
-        t.host_exec_max = (int64_t)value << 10;
-    }
-    else if (k == "host_buffers") {
-        if (value < 1 || value > 8) return ECX_E_ILLEGAL_ARGUMENT;
-        t.host_buffers = value;
-    }
-    else return ECX_E_ILLEGAL_ARGUMENT;
-    return ECX_OK;
 }
 }  // namespace
 
 int ecx_tune(const char *key, int value) {
-    const std::string k = key ? key : "";
-    int rc = ECX_OK;
-    update_tuning([&](Tuning &t) { rc = set_tune(t, k, value); });
-    return rc;
+    // ECX_SHAPE_KNOBS is read once, so one library loaded into a JVM cannot be talked into reshaping
+    // every other caller's launches later on; ECX_DIAGNOSTIC with every call
+    static const bool shape_opt_in = env_is_1("ECX_SHAPE_KNOBS");
+    const KnobEnv env{ECX_DIAG != 0, shape_opt_in, env_is_1("ECX_DIAGNOSTIC")};
+    const Knob *k = find_knob(key);
+    bool ok = false;
+    update_tuning([&](Tuning &t) { ok = k && knob_set(t, *k, value, env); });
+    if (ok && k->store == KnobStore::external) g_roctx.store(value);  // "roctx"
+    return ok ? ECX_OK : ECX_E_ILLEGAL_ARGUMENT;
 }
 
 int ecx_tune_value(const char *key, int *value) {
-    const std::string k = key ? key : "";
-    if (!value || !deployment_key(k)) return ECX_E_ILLEGAL_ARGUMENT;
-    const Tuning t = tuning();
-    if (k == "host_chunk_kib") *value = (int)(t.host_chunk >> 10);
-    else if (k == "host_buffers") *value = t.host_buffers;
-    else if (k == "host_gather_kib") *value = (int)(t.host_gather_max >> 10);
-    else if (k == "host_zero_copy") *value = t.host_zero_copy;
-    else if (k == "host_contexts") *value = t.host_contexts;
-    else if (k == "host_exec_kib") *value = (int)(t.host_exec_max >> 10);
-    else if (k == "roctx") *value = g_roctx.load();
-    else if (k == "plan_cache") *value = t.plan_cache;
-    else *value = t.layout_select;  // deployment_key: the only one left
+    const Knob *k = find_knob(key);
+    if (!value || !k || k->cls != KnobClass::deployment) return ECX_E_ILLEGAL_ARGUMENT;
+    if (!knob_get(tuning(), *k, value)) *value = g_roctx.load();  // "roctx"
     return ECX_OK;
 }
 
@@ -1995,5 +1760,3 @@ int ecx_count_mismatch(const uint8_t *a, int64_t a_stride, const uint8_t *b, int
         return ECX_OK;
     });
 }
-
-}  // extern "C"
