@@ -266,6 +266,38 @@ int ecx_rs_is_parity_correct_blocked_batch_host_devices(ecx_rs *rs, const uint8_
                                                         int64_t byte_count, int64_t block_bytes, uint8_t *verdict,
                                                         const int *devices, int ndev);
 
+/* decodeMissing (ReedSolomon.java:189-286) per stripe over the blocked layout, in place: stripe s of
+ * the nstripes stripes at base (body [nstripes][full][n][block], then tails [nstripes][n][tail];
+ * block_bytes 0 = the recommended block) is decoded with pattern pattern_of_stripe[s], a DEVICE
+ * byte array of nstripes.  An id with no pattern, or a pattern with nothing missing, leaves every
+ * byte of that stripe untouched, body and tail.  Each pass of the layout is one launch; a block
+ * row finds its stripe's id as unit / full on the device.  Only enqueues.  Checked in this order:
+ * null set ECX_E_NULL; negative nstripes or byte_count ECX_E_ILLEGAL_ARGUMENT; null base or
+ * pattern_of_stripe ECX_E_NULL; negative block_bytes or an extent beyond int64_t
+ * ECX_E_ILLEGAL_ARGUMENT; nstripes == 0 or byte_count == 0 enqueues nothing. */
+int ecx_rs_decode_missing_blocked_batch_mixed(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                              uint8_t *base, int64_t nstripes, int64_t byte_count,
+                                              int64_t block_bytes, void *stream);
+/* decodeMissing (ReedSolomon.java:189-286) per stripe over HOST-memory stripes, in place, layout
+ * and meaning of ecx_rs_decode_missing_batch_mixed: base and pattern_of_stripe are host pointers
+ * (pageable or pinned).  Synchronous, on the current device: the ids go to the device once, then
+ * chunks of stripes are pipelined H2D -> mixed launch -> D2H.  D2H returns the union of the
+ * patterns' output shards for every stripe, so H2D carries that union as well as every shard a
+ * pattern reads (up to n shards up instead of k): a shard one pattern rebuilds comes back
+ * unchanged for the stripes of the other patterns.  Present shards, untouched stripes and bytes
+ * outside [offset, offset + byte_count) are bit-identical afterwards.  A batch of no stripes needs
+ * no buffers; without a usable device a batch with work returns ECX_E_DEVICE. */
+int ecx_rs_decode_missing_mixed_batch_host(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                           uint8_t *base, int64_t stripe_stride, int64_t shard_stride,
+                                           int64_t nstripes, int64_t offset, int64_t byte_count);
+/* decodeMissing (ReedSolomon.java:189-286) per stripe over HOST-memory stripes in the blocked
+ * layout, in place: ecx_rs_decode_missing_blocked_batch_mixed with host pointers, each pass of the
+ * layout a pipelined host batch as ecx_rs_decode_missing_mixed_batch_host (the ids cross once for
+ * both; a chunk of block rows may begin mid-stripe).  Synchronous, on the current device. */
+int ecx_rs_decode_missing_blocked_mixed_batch_host(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                                   uint8_t *base, int64_t nstripes, int64_t byte_count,
+                                                   int64_t block_bytes);
+
 /* As ecx_map_apply_batch, but XOR-accumulates: out ^= M * in. */
 int ecx_map_accumulate_batch(const ecx_map *map, const uint8_t *in, int64_t in_stripe_stride,
                              int64_t in_slot_stride, uint8_t *out, int64_t out_stripe_stride, int64_t out_slot_stride,

@@ -77,6 +77,35 @@ public final class EcxMixedDecode {
                 nstripes, offset, byteCount, stream));
     }
 
+    /**
+     * decodeMissingBatch over nstripes device-resident stripes in the blocked layout
+     * (EcxBlockedStripes; body [nstripes][full][n][block], then tails [nstripes][n][tail]), in
+     * place: stripe s is decoded with pattern patternOfStripe[s] (a device byte array of
+     * nstripes).  blockBytes 0 = the recommended block.  Only enqueues on {@code stream}.
+     */
+    public void decodeMissingBlockedBatch(long patternOfStripe, long base, long nstripes, long byteCount,
+                                          long blockBytes, long stream) {
+        Ecx.check(EcxNative.rsDecodeMissingBlockedBatchMixed(handle(), patternOfStripe, base, nstripes, byteCount,
+                blockBytes, stream));
+    }
+
+    /**
+     * decodeMissingBatch over HOST-memory stripes at raw addresses, synchronous.  Package-private:
+     * a raw host address carries no capacity to check (no ByteBuffer form yet; INTEGRATION.md).
+     */
+    void decodeMissingBatchHost(long patternOfStripe, long base, long stripeStride, long shardStride, long nstripes,
+                                long offset, long byteCount) {
+        Ecx.check(EcxNative.rsDecodeMissingMixedBatchHost(handle(), patternOfStripe, base, stripeStride, shardStride,
+                nstripes, offset, byteCount));
+    }
+
+    /** decodeMissingBlockedBatch over HOST-memory stripes at raw addresses, synchronous; package-private likewise. */
+    void decodeMissingBlockedBatchHost(long patternOfStripe, long base, long nstripes, long byteCount,
+                                       long blockBytes) {
+        Ecx.check(EcxNative.rsDecodeMissingBlockedMixedBatchHost(handle(), patternOfStripe, base, nstripes, byteCount,
+                blockBytes));
+    }
+
     /** {patterns, shards per stripe, most shards any pattern misses}. */
     public int[] info() {
         int[] n = new int[1], shards = new int[1], missing = new int[1];

@@ -139,6 +139,11 @@ RULES = {
     # (pattern_of_stripe and base are longs, like every *_batch pointer)
     "ecx_rs_pattern_set_create": (("rs",), [NN("npatterns"), A("patterns", "(int64_t)npatterns * (%s)" % RS_N)]),
     "ecx_rs_pattern_set_info": ((), [A("npatterns", "1"), A("shards", "1"), A("max_missing", "1")]),
+    # the blocked and the host-memory mixed decodes take addresses only as well (the host forms'
+    # natives are package-private: "_batch_host"); their counts are refused here as the exports do
+    "ecx_rs_decode_missing_blocked_batch_mixed": ((), [NN("nstripes", "byte_count")]),
+    "ecx_rs_decode_missing_mixed_batch_host": ((), [NN("nstripes", "offset", "byte_count")]),
+    "ecx_rs_decode_missing_blocked_mixed_batch_host": ((), [NN("nstripes", "byte_count")]),
     # the index helper: nstripes rows of `shards` flags in, up to cap rows and nstripes ids out
     "ecx_rs_index_patterns": ((), [NN("shards", "nstripes", "cap"), A("present", "(int64_t)nstripes * shards"),
                                    A("patterns", "(int64_t)cap * shards"), A("npatterns", "1"),

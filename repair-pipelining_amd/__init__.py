@@ -847,6 +847,45 @@ class ReedSolomon:
         check(lib().ecx_rs_decode_missing_batch_mixed(patternSet._h, _dev_ptr(ids), _dev_ptr(shards), stripe_stride,
                                                       shard_stride, nstripes, offset, byteCount, _stream(stream)))
 
+    def _check_pattern_set(self, patternSet):
+        if patternSet._h is None:
+            raise EcxError(-6, "the pattern set is closed")
+        if patternSet.totalShardCount != self.getTotalShardCount():
+            raise EcxError(-1, "the pattern set belongs to another code")
+
+    def decodeMissingBlockedBatchMixed(self, base, patternSet, ids, nstripes, byteCount, blockBytes=0, stream=None):
+        """decodeMissingBatchMixed over nstripes device-resident stripes in the blocked layout, in
+        place (ecx_rs_decode_missing_blocked_batch_mixed; blockBytes 0 = the recommended block):
+        stripe s is decoded with pattern ``ids[s]`` of ``patternSet``; ``ids`` is a device uint8
+        array of nstripes.  An id without a pattern, or a pattern with nothing missing, leaves its
+        stripe untouched, body and tail."""
+        self._check_pattern_set(patternSet)
+        _check_extent(base, nstripes * self.getTotalShardCount() * byteCount, "base")
+        _check_layout(ids, 1, 0, 0, nstripes, 1, "ids")
+        check(lib().ecx_rs_decode_missing_blocked_batch_mixed(patternSet._h, _dev_ptr(ids), _dev_ptr(base), nstripes,
+                                                              byteCount, blockBytes, _stream(stream)))
+
+    def decodeMissingBatchMixedHost(self, shards, patternSet, ids, stripe_stride, shard_stride, nstripes, offset,
+                                    byteCount):
+        """decodeMissingBatchMixed over HOST-memory stripes, in place and synchronous
+        (ecx_rs_decode_missing_mixed_batch_host): ``shards`` and ``ids`` (uint8, nstripes) are
+        host buffers, pageable or pinned."""
+        self._check_pattern_set(patternSet)
+        _check_layout(shards, stripe_stride, shard_stride, self.getTotalShardCount() - 1, nstripes, offset + byteCount,
+                      "shards")
+        _check_layout(ids, 1, 0, 0, nstripes, 1, "ids")
+        check(lib().ecx_rs_decode_missing_mixed_batch_host(patternSet._h, _host_ptr(ids), _host_ptr(shards),
+                                                           stripe_stride, shard_stride, nstripes, offset, byteCount))
+
+    def decodeMissingBlockedBatchMixedHost(self, base, patternSet, ids, nstripes, byteCount, blockBytes=0):
+        """decodeMissingBlockedBatchMixed over HOST-memory stripes in the blocked layout, in place
+        and synchronous (ecx_rs_decode_missing_blocked_mixed_batch_host)."""
+        self._check_pattern_set(patternSet)
+        _check_extent(base, nstripes * self.getTotalShardCount() * byteCount, "base")
+        _check_layout(ids, 1, 0, 0, nstripes, 1, "ids")
+        check(lib().ecx_rs_decode_missing_blocked_mixed_batch_host(patternSet._h, _host_ptr(ids), _host_ptr(base),
+                                                                   nstripes, byteCount, blockBytes))
+
     def decodePartialBatch(self, shardPresent, shardIndex, inp, in_stripe_stride, acc, acc_stripe_stride,
                            acc_row_stride, nstripes, byteCount, isFirst, stream=None):
         """Batched decodeMissingSingle for every missing shard (data and parity)."""

@@ -122,6 +122,9 @@ SIGNATURES = {
     "ecx_rs_pattern_set_destroy": (None, [P]),
     "ecx_rs_pattern_set_info": (I, [P, PI, PI, PI]),
     "ecx_rs_decode_missing_batch_mixed": (I, [P, P, P, I64, I64, I64, I64, I64, P]),
+    "ecx_rs_decode_missing_blocked_batch_mixed": (I, [P, P, P, I64, I64, I64, P]),
+    "ecx_rs_decode_missing_mixed_batch_host": (I, [P, P, P, I64, I64, I64, I64, I64]),
+    "ecx_rs_decode_missing_blocked_mixed_batch_host": (I, [P, P, P, I64, I64, I64]),
     "ecx_rs_index_patterns": (I, [I, P, I64, P, I, PI, P]),
     "ecx_rs_decode_partial_batch": (I, [P, P, I, P, I64, P, I64, I64, I64, I64, I, P]),
     "ecx_rs_encode_partial_batch": (I, [P, I, P, I64, P, I64, I64, I64, I64, I, P]),

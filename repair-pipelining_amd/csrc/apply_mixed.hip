@@ -12,10 +12,16 @@
 //
 // The id array is device memory written by an earlier kernel or copy of the caller's stream, so
 // it is read with an ordinary global load, not through the constant address space the plan uses.
+//
+// Over the blocked RS layout (blocked_layout.hpp) the same body runs as
+// k_gf_apply_mixed_blocked: a launch's units are the block rows of the layout's body pass, `full`
+// consecutive ones per caller stripe, and a unit takes the id of stripe unit / full
+// (launch_apply_mixed_units; mixed_launch.hpp cuts a pass into launches).
 #include <algorithm>
 
 #include "apply.hpp"
 #include "layout_probe.hpp"  // note_device_launch
+#include "mixed_launch.hpp"
 #include "pattern_set.hpp"
 
 namespace ecx {
@@ -41,9 +47,43 @@ __global__ void __launch_bounds__(kBlockThreads, ECX_APPLY_BOUNDS(ROWS, DEPTH)) 
         uniform64((uint64_t)(a.out + s * a.out_stripe_stride + cbase)), threadIdx.x * 16, valid, nullptr);
 }
 
+// The same body over one pass of a blocked batch (blocked_layout.hpp, mixed_launch.hpp): the
+// launch's units are block rows, vd.divisor consecutive ones per caller stripe, so the pattern id
+// of a unit is that of stripe unit / divisor.  `ids` points at the id of the launch's first
+// unit's stripe and vd.rem is that unit's place in it.  The unit comes from the block index and is
+// made wave-uniform first, so the quotient is two scalar multiplies (verdict_quot; gfx950 has no
+// scalar divide) ahead of the id load.  A kernel of its own, as k_gf_check_blocked is: the
+// natural layout's instances stay what they were.
+template <bool SAFE, int DEPTH, int ROWS>
+__global__ void __launch_bounds__(kBlockThreads, ECX_APPLY_BOUNDS(ROWS, DEPTH))
+    k_gf_apply_mixed_blocked(ApplyArgs a, const uint8_t *ids, VerdictDiv vd) {
+    const uint32_t nc = (uint32_t)a.n_chunks;
+    const uint32_t local_unit = __builtin_amdgcn_readfirstlane(blockIdx.x / nc);
+    const int64_t s = (int64_t)local_unit + a.stripe_begin;
+    const int64_t c = (int64_t)(blockIdx.x % nc) + a.chunk_begin;
+    const uint32_t id = __builtin_amdgcn_readfirstlane((uint32_t)((const gu8 *)ids)[verdict_quot(vd, local_unit)]);
+    cu32 *tile = plan_ptr(a.tiles) + id * kTileDwords;
+    if (tile[2] == 0) return;  // wave-uniform: the whole workgroup leaves
+    const int64_t cbase = c * kChunkBytes;
+    int valid = 16;
+    if (SAFE) {
+        const int64_t v = a.nbytes - cbase - (int64_t)threadIdx.x * 16;
+        valid = v <= 0 ? 0 : (v >= 16 ? 16 : (int)v);
+    }
+    apply_tile<SAFE, true, SAFE ? 0 : 1, DEPTH, false, kBlockThreads, ROWS>(
+        a, tile, uniform64((uint64_t)(a.in + s * a.in_stripe_stride + cbase)),
+        uniform64((uint64_t)(a.out + s * a.out_stripe_stride + cbase)), threadIdx.x * 16, valid, nullptr);
+}
+
 namespace {
+// vd null: the units are the stripes, k_gf_apply_mixed reads ids[unit]
 template <bool SAFE, int D, int R>
-void launch_mixed_k(dim3 grid, hipStream_t stream, const ApplyArgs &a, const uint8_t *ids) {
+void launch_mixed_k(dim3 grid, hipStream_t stream, const ApplyArgs &a, const uint8_t *ids, const VerdictDiv *vd) {
+    if (vd) {
+        if (!SAFE) note_kernel("k_gf_apply_mixed_blocked", SAFE, D, R);
+        hipLaunchKernelGGL((k_gf_apply_mixed_blocked<SAFE, D, R>), grid, dim3(kBlockThreads), 0, stream, a, ids, *vd);
+        return;
+    }
     if (!SAFE) note_kernel("k_gf_apply_mixed", SAFE, D, R);
     hipLaunchKernelGGL((k_gf_apply_mixed<SAFE, D, R>), grid, dim3(kBlockThreads), 0, stream, a, ids);
 }
@@ -54,9 +94,17 @@ void launch_mixed_k(dim3 grid, hipStream_t stream, const ApplyArgs &a, const uin
 // either plan is padded to a multiple of 4 -- and 8 rows) for the partial last chunk and every
 // other layout.
 // There is no per-layout shape selection here: the work differs from stripe to stripe.
-void launch_apply_mixed(PatternSet &set, const uint8_t *ids, uint8_t *base, int64_t stripe_stride,
-                        int64_t slot_stride, int64_t nstripes, int64_t nbytes, hipStream_t stream) {
-    if (nstripes <= 0 || nbytes <= 0 || set.max_rows() == 0) return;
+//
+// The pass is `units` units of which `divisor` consecutive ones are one caller stripe, and its
+// first unit is unit `first_unit` of the whole pass `ids` describes: ids[(first_unit + u) / divisor]
+// is unit u's pattern.  Divisor 1 (a natural batch, a blocked batch's tails, a body of one block
+// per stripe) runs k_gf_apply_mixed, anything else k_gf_apply_mixed_blocked; mixed_launch.hpp
+// cuts the pass into launches.
+void launch_apply_mixed_units(PatternSet &set, const uint8_t *ids, uint8_t *base, int64_t stripe_stride,
+                              int64_t slot_stride, int64_t units, int64_t nbytes, int64_t divisor,
+                              int64_t first_unit, hipStream_t stream) {
+    if (units <= 0 || nbytes <= 0 || set.max_rows() == 0) return;
+    if (divisor < 1 || first_unit < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "bad unit divisor");
     // the set's own ring depth, or the one ecx_tune "depth" forces (4 / 8; others have no instance)
     const Tuning tu = tuning();
     const int depth = tu.depth == 4 || tu.depth == 8 ? tu.depth : set.preferred_depth();
@@ -68,11 +116,10 @@ void launch_apply_mixed(PatternSet &set, const uint8_t *ids, uint8_t *base, int6
     const int rows = hp.max_rows <= 4 ? 4 : kTileRows;
     // in place: the alignment conditions of a full-chunk launch are launch_rules' (BatchLayout)
     const BatchLayout b{(uintptr_t)base, (uintptr_t)base, stripe_stride, slot_stride, stripe_stride,
-                        slot_stride,     nstripes,        nbytes,        false};
+                        slot_stride,     units,           nbytes,        false};
     const int64_t full = b.aligned16() ? nbytes / kChunkBytes : 0;
     const int64_t rest = (nbytes - full * kChunkBytes + kChunkBytes - 1) / kChunkBytes;
-    const int64_t max_blocks = (int64_t)1 << 30;
-    if (full + rest > max_blocks) throw Error(ECX_E_ILLEGAL_ARGUMENT, "byte_count is too large for one launch");
+    if (full + rest > kMixedMaxBlocks) throw Error(ECX_E_ILLEGAL_ARGUMENT, "byte_count is too large for one launch");
 
     ApplyArgs a{};
     a.in = base;
@@ -89,16 +136,18 @@ void launch_apply_mixed(PatternSet &set, const uint8_t *ids, uint8_t *base, int6
         if (n_chunks <= 0) return;
         a.chunk_begin = chunk_begin;
         a.n_chunks = n_chunks;
-        const int64_t stripes_per_launch = std::max<int64_t>(1, max_blocks / n_chunks);
-        for (int64_t s0 = 0; s0 < nstripes; s0 += stripes_per_launch) {
-            a.stripe_begin = s0;
-            const dim3 grid((unsigned)(std::min(stripes_per_launch, nstripes - s0) * n_chunks));
-            if (safe) launch_mixed_k<true, 4, kTileRows>(grid, stream, a, ids);
-            else if (rows == 4 && depth == 8) launch_mixed_k<false, 8, 4>(grid, stream, a, ids);
-            else if (rows == 4) launch_mixed_k<false, 4, 4>(grid, stream, a, ids);
-            else if (depth == 8) launch_mixed_k<false, 8, kTileRows>(grid, stream, a, ids);
-            else launch_mixed_k<false, 4, kTileRows>(grid, stream, a, ids);
-        }
+        for_mixed_launches(units, n_chunks, divisor, first_unit, kMixedMaxBlocks, [&](const MixedLaunch &l) {
+            a.stripe_begin = l.unit_begin;
+            const dim3 grid((unsigned)(l.unit_count * n_chunks));
+            // divisor 1: k_gf_apply_mixed indexes its ids by unit_begin + the local unit itself
+            const uint8_t *lids = divisor > 1 ? ids + l.id_begin : ids + first_unit;
+            const VerdictDiv *vd = divisor > 1 ? &l.vd : nullptr;
+            if (safe) launch_mixed_k<true, 4, kTileRows>(grid, stream, a, lids, vd);
+            else if (rows == 4 && depth == 8) launch_mixed_k<false, 8, 4>(grid, stream, a, lids, vd);
+            else if (rows == 4) launch_mixed_k<false, 4, 4>(grid, stream, a, lids, vd);
+            else if (depth == 8) launch_mixed_k<false, 8, kTileRows>(grid, stream, a, lids, vd);
+            else launch_mixed_k<false, 4, kTileRows>(grid, stream, a, lids, vd);
+        });
     };
     run(false, 0, full);
     run(true, full, rest);
@@ -108,7 +157,29 @@ void launch_apply_mixed(PatternSet &set, const uint8_t *ids, uint8_t *base, int6
     // (input bytes, for the launch registry: as if every stripe read its longest pattern)
     uint32_t inputs = 0;
     for (int p = 0; p < hp.npatterns; ++p) inputs = std::max(inputs, hp.tiles[(size_t)p * kTileDwords + 3]);
-    note_device_launch(dev, stream, nstripes * nbytes * (int64_t)inputs);
+    note_device_launch(dev, stream, units * nbytes * (int64_t)inputs);
+}
+
+void launch_apply_mixed(PatternSet &set, const uint8_t *ids, uint8_t *base, int64_t stripe_stride,
+                        int64_t slot_stride, int64_t nstripes, int64_t nbytes, hipStream_t stream) {
+    launch_apply_mixed_units(set, ids, base, stripe_stride, slot_stride, nstripes, nbytes, 1, 0, stream);
+}
+
+// A mixed decode over a blocked batch: the layout's passes in order, each with its divisor.  The
+// first pass makes the set's plan resident before it enqueues anything, so a first use refused
+// under capture leaves no node of either pass behind.
+void launch_apply_mixed_blocked(PatternSet &set, const uint8_t *ids, uint8_t *base, const BlockedPlan &plan,
+                                hipStream_t stream) {
+    std::string body_kernel;
+    for (int i = 0; i < plan.count; ++i) {
+        const BlockedPass &p = plan.pass[i];
+        const uint64_t notes0 = kernel_notes();
+        launch_apply_mixed_units(set, ids, base + p.offset, p.stripe_stride, p.slot_bytes, p.units, p.slot_bytes,
+                                 p.divisor, 0, stream);
+        if (i == 0 && kernel_notes() != notes0) body_kernel = last_kernel();
+    }
+    // the launch of record is the first pass's (the body, nearly all of the bytes), not the tails'
+    if (plan.count > 1 && !body_kernel.empty()) set_last_kernel(body_kernel);
 }
 
 }  // namespace ecx

@@ -804,6 +804,66 @@ int ecx_rs_decode_missing_blocked_batch_host_devices(ecx_rs *rs, const uint8_t *
                             {true, true, nullptr, devices, ndev});
 }
 
+namespace {
+// The one body of the two blocked mixed decodes (ecx.h); tests/test_mixed_blocked_cpu.py pins the
+// order of its checks.  Each pass of the layout is a mixed launch with the pass's divisor -- from
+// host memory a pipelined host batch of its own, the ids on the device once for both.
+int rs_mixed_blocked(const char *fn, const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe, uint8_t *base,
+                     int64_t nstripes, int64_t byte_count, int64_t block_bytes, bool host, void *stream) {
+    return guarded(fn, [&]() -> int {
+        if (!set) throw Error(ECX_E_NULL, "null pattern set");
+        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        // a host batch of no stripes needs no buffers
+        if ((!base || !pattern_of_stripe) && (!host || nstripes > 0))
+            throw Error(ECX_E_NULL, host ? "null host pointer" : "null device pointer");
+        const int n = set->rs->code.n();
+        const int64_t block = resolve_block(n, byte_count, block_bytes);
+        BlockedPlan plan;
+        blocked_plan_or_throw(n, nstripes, byte_count, block, &plan);
+        if (plan.count == 0 || set->set->max_rows() == 0) return ECX_OK;  // no bytes, or nothing missing anywhere
+        if (!host) {
+            launch_apply_mixed_blocked(*set->set, pattern_of_stripe, base, plan, (hipStream_t)stream);
+            return ECX_OK;
+        }
+        const HostMixedIds ids(pattern_of_stripe, nstripes);
+        for (int i = 0; i < plan.count; ++i) {
+            const BlockedPass &p = plan.pass[i];
+            run_host_mixed_batch(*set->set, ids.get(), base + p.offset, p.stripe_stride, p.slot_bytes, n, p.units,
+                                 p.slot_bytes, p.divisor);
+        }
+        return ECX_OK;
+    });
+}
+}  // namespace
+
+int ecx_rs_decode_missing_blocked_batch_mixed(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                              uint8_t *base, int64_t nstripes, int64_t byte_count,
+                                              int64_t block_bytes, void *stream) {
+    return rs_mixed_blocked(__func__, set, pattern_of_stripe, base, nstripes, byte_count, block_bytes, false, stream);
+}
+
+int ecx_rs_decode_missing_blocked_mixed_batch_host(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                                   uint8_t *base, int64_t nstripes, int64_t byte_count,
+                                                   int64_t block_bytes) {
+    return rs_mixed_blocked(__func__, set, pattern_of_stripe, base, nstripes, byte_count, block_bytes, true, nullptr);
+}
+
+int ecx_rs_decode_missing_mixed_batch_host(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                           uint8_t *base, int64_t stripe_stride, int64_t shard_stride,
+                                           int64_t nstripes, int64_t offset, int64_t byte_count) {
+    return guarded(__func__, [&]() -> int {
+        if (!set) throw Error(ECX_E_NULL, "null pattern set");
+        if (nstripes < 0 || offset < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        if ((!base || !pattern_of_stripe) && nstripes > 0) throw Error(ECX_E_NULL, "null host pointer");
+        if (nstripes == 0 || byte_count == 0 || set->set->max_rows() == 0) return ECX_OK;
+        if (stripe_stride < 0 || shard_stride < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative stride");
+        const HostMixedIds ids(pattern_of_stripe, nstripes);
+        run_host_mixed_batch(*set->set, ids.get(), base + offset, stripe_stride, shard_stride, set->rs->code.n(),
+                             nstripes, byte_count, 1);
+        return ECX_OK;
+    });
+}
+
 int ecx_rs_encode_parity(ecx_rs *rs, uint8_t *const *shards, int shard_count, int shard_length, int offset,
                          int byte_count) {
     return guarded(__func__, [&]() -> int {

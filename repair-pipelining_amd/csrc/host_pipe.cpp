@@ -18,11 +18,15 @@
 // other progressions of equal runs in one 3D copy each, a one-chunk batch of
 // huge stripes cut into column slices, and over a device list, few stripes
 // split by byte ranges (ecx_map_host_plan reports the plan).
+//
+// run_host_mixed_batch is the same ring for a pattern set decoded in place:
+// the union of the patterns' slots goes up, the union of their output slots comes back.
 #include <algorithm>
 #include <cstring>
 #include <thread>
 
 #include "host_pipe.hpp"
+#include "pattern_set.hpp"
 
 namespace ecx {
 namespace {
@@ -453,6 +457,73 @@ void run_host_check_batch(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_
             check_hip(hipEventRecord(b.drained, p.d2h), "hipEventRecord");
         }
         check_hip(hipStreamSynchronize(p.d2h), "hipStreamSynchronize (host check batch)");
+    } catch (...) {
+        p.drain();
+        throw;
+    }
+}
+
+HostMixedIds::HostMixedIds(const uint8_t *host_ids, int64_t nstripes) {
+    if (nstripes <= 0) return;
+    check_hip(hipMalloc(&dev_, (size_t)nstripes), "hipMalloc (pattern ids)");
+    if (hipMemcpy(dev_, host_ids, (size_t)nstripes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev_);
+        dev_ = nullptr;
+        throw Error(ECX_E_DEVICE, "hipMemcpy (pattern ids)");
+    }
+}
+
+HostMixedIds::~HostMixedIds() {
+    if (dev_) (void)hipFree(dev_);
+}
+
+// The in-place twin of run_host_batch for a pattern set.  The plan of a set addresses slots by
+// their shard index (each pattern its own), so a set's buffer keeps all n slots of a unit at the
+// pass's own pitch and only the copies are sparse: up_slots go H2D, the mixed launch runs over
+// the buffer in place with the chunk's first unit (a chunk may begin mid-stripe: the launcher
+// finds each unit's id through the divisor), and down_slots come back.  Chunks are sized by the
+// bytes that go up, like run_host_batch's.  up_slots contains down_slots (pattern_set.hpp): a
+// down slot comes back for every stripe, also for one whose pattern leaves it alone, and must
+// then carry that stripe's own bytes.
+void run_host_mixed_batch(PatternSet &set, const uint8_t *dev_ids, uint8_t *base, int64_t stripe_stride,
+                          int64_t slot_stride, int n, int64_t units, int64_t nbytes, int64_t divisor) {
+    if (units <= 0 || nbytes <= 0 || set.down_slots().empty()) return;
+    const int64_t per = (int64_t)n * nbytes;  // a unit on the device: [slot][nbytes], every slot
+    auto device_runs = [&](const std::vector<int> &slots) {
+        std::vector<Run> runs = runs_of(slots, slot_stride, nbytes);
+        for (Run &r : runs) r.compact0 = r.slot0;  // not compacted
+        return runs;
+    };
+    const std::vector<Copy> cin = plan_copies(device_runs(set.up_slots()), stripe_stride, slot_stride, per, nbytes);
+    const std::vector<Copy> cout = plan_copies(device_runs(set.down_slots()), stripe_stride, slot_stride, per, nbytes);
+    const Tuning &t = tuning();
+    const int64_t up_per = (int64_t)set.up_slots().size() * nbytes;
+    constexpr int64_t kMinRows = 160;  // as make_plan
+    int64_t chunk = t.host_chunk / std::max<int64_t>(1, up_per);
+    if (cin.size() > 8) chunk = std::max(chunk, std::min(kMinRows, 8 * t.host_chunk / std::max<int64_t>(1, up_per)));
+    chunk = std::max<int64_t>(1, std::min<int64_t>(units, chunk));
+    const int64_t nchunks = (units + chunk - 1) / chunk;
+    const int nb = (int)std::min<int64_t>(std::max(1, std::min(t.host_buffers, 8)), nchunks);
+
+    HostPipe &p = HostPipe::current();
+    std::lock_guard<std::mutex> lk(p.mu);
+    try {
+        p.ensure(nb, (size_t)(chunk * per), 0);
+        for (int64_t i = 0; i < nchunks; ++i) {
+            HostPipe::Set &b = p.sets[(size_t)(i % nb)];
+            const int64_t lo = i * chunk, cnt = std::min(chunk, units - lo);
+            uint8_t *host = base + lo * stripe_stride;
+            if (i >= nb) check_hip(hipStreamWaitEvent(p.h2d, b.drained, 0), "hipStreamWaitEvent");
+            for (const Copy &c : cin) issue_copy(c, host, b.in, stripe_stride, per, cnt, hipMemcpyHostToDevice, p.h2d);
+            check_hip(hipEventRecord(b.loaded, p.h2d), "hipEventRecord");
+            check_hip(hipStreamWaitEvent(p.cmp, b.loaded, 0), "hipStreamWaitEvent");
+            launch_apply_mixed_units(set, dev_ids, b.in, per, nbytes, cnt, nbytes, divisor, lo, p.cmp);
+            check_hip(hipEventRecord(b.computed, p.cmp), "hipEventRecord");
+            check_hip(hipStreamWaitEvent(p.d2h, b.computed, 0), "hipStreamWaitEvent");
+            for (const Copy &c : cout) issue_copy(c, host, b.in, stripe_stride, per, cnt, hipMemcpyDeviceToHost, p.d2h);
+            check_hip(hipEventRecord(b.drained, p.d2h), "hipEventRecord");
+        }
+        check_hip(hipStreamSynchronize(p.d2h), "hipStreamSynchronize (host mixed batch)");
     } catch (...) {
         p.drain();
         throw;

@@ -1,6 +1,8 @@
 // pattern_set.cpp -- a pattern set's host plans and their per-device upload (pattern_set.hpp).
 #include "pattern_set.hpp"
 
+#include <set>
+
 namespace ecx {
 
 PatternSet::PatternSet(const std::vector<const CompiledMap *> &maps) {
@@ -18,6 +20,20 @@ PatternSet::PatternSet(const std::vector<const CompiledMap *> &maps) {
     if (!build_mixed_plan(in.data(), (int)in.size(), 4, &plan4_) || !build_mixed_plan(in.data(), (int)in.size(), 8, &plan8_))
         throw Error(ECX_E_ILLEGAL_ARGUMENT, "a pattern set holds 1.." + std::to_string(kMixedRecords) + " patterns");
     preferred_depth_ = mixed_depth(in.data(), (int)in.size());
+    // the slots a host batch moves: every record's output slots down; those and every slot an entry
+    // loads up (pattern_set.hpp)
+    std::set<int> up, down;
+    for (int p = 0; p < plan4_.npatterns; ++p) {
+        const uint32_t *tile = plan4_.tiles.data() + (size_t)p * kTileDwords;
+        for (uint32_t r = 0; r < tile[2]; ++r) down.insert((int)tile[4 + r]);
+        for (uint32_t e = 0; e < tile[1]; ++e) {
+            const uint32_t slot = plan4_.entries[((size_t)tile[0] + e) * kEntryDwords];
+            if (tile[2] != 0 && slot != kDummySlot) up.insert((int)slot);
+        }
+    }
+    up.insert(down.begin(), down.end());
+    up_slots_.assign(up.begin(), up.end());
+    down_slots_.assign(down.begin(), down.end());
 }
 
 PatternSet::~PatternSet() {

@@ -4,6 +4,7 @@
 // name their pattern with one byte each (apply_mixed.hip).
 #pragma once
 
+#include "blocked_layout.hpp"
 #include "engine.hpp"
 #include "mixed_plan.hpp"
 
@@ -33,6 +34,12 @@ public:
     int preferred_depth() const { return preferred_depth_; }
     const MixedPlan &plan(int depth) const { return depth == 8 ? plan8_ : plan4_; }
     int max_rows() const { return plan4_.max_rows; }
+    // What a host batch moves (host_pipe.cpp run_host_mixed_batch), sorted: down_slots is the union
+    // of the patterns' output slots, up_slots the union of every pattern's input AND output slots.
+    // A stripe gets every down slot back, also one its own pattern leaves alone, so each of them
+    // must have gone up for every stripe even where no pattern reads it.
+    const std::vector<int> &up_slots() const { return up_slots_; }
+    const std::vector<int> &down_slots() const { return down_slots_; }
     // The plan uploaded for the current device, lazily, like CompiledMap::plan_for_current_device.
     // A first-use site: refused on a capturing stream (engine.hpp refuse_if_capturing).
     const MixedDevicePlan &plan_for_current_device(int depth);
@@ -40,6 +47,7 @@ public:
 private:
     MixedPlan plan4_, plan8_;
     int preferred_depth_ = 4;
+    std::vector<int> up_slots_, down_slots_;
     std::mutex mu_;
     std::map<std::pair<int, int>, MixedDevicePlan> dev_;  // (device, depth)
 };
@@ -50,5 +58,38 @@ private:
 // leaves its stripe untouched.
 void launch_apply_mixed(PatternSet &set, const uint8_t *ids, uint8_t *base, int64_t stripe_stride,
                         int64_t slot_stride, int64_t nstripes, int64_t nbytes, hipStream_t stream);
+// The general form: `units` units of [unit][slot][bytes] at `base`, `divisor` consecutive ones per
+// caller stripe (a pass of a blocked batch, blocked_layout.hpp), the first of them unit
+// `first_unit` of the whole pass -- a chunk of the host pipeline may begin mid-stripe.  `ids` is
+// the id of the whole pass's first stripe: unit u runs record ids[(first_unit + u) / divisor].
+// Divisor 1 is launch_apply_mixed's kernel; above it k_gf_apply_mixed_blocked divides on the
+// device (mixed_launch.hpp has the split into launches).
+void launch_apply_mixed_units(PatternSet &set, const uint8_t *ids, uint8_t *base, int64_t stripe_stride,
+                              int64_t slot_stride, int64_t units, int64_t nbytes, int64_t divisor,
+                              int64_t first_unit, hipStream_t stream);
+// Every pass of a blocked batch at `base`, in place; `ids` is a device byte array of the batch's
+// caller stripes.
+void launch_apply_mixed_blocked(PatternSet &set, const uint8_t *ids, uint8_t *base, const BlockedPlan &plan,
+                                hipStream_t stream);
+
+// The mixed decode over HOST memory (host_pipe.cpp), synchronous, in place, on the current
+// device: one pass of `units` units of n slots of nbytes bytes (stripe_stride / slot_stride apart
+// in host memory), `divisor` units per caller stripe; `dev_ids` is the device copy of the caller's
+// ids.  Chunks of units go H2D (up_slots), through launch_apply_mixed_units, and D2H (down_slots).
+void run_host_mixed_batch(PatternSet &set, const uint8_t *dev_ids, uint8_t *base, int64_t stripe_stride,
+                          int64_t slot_stride, int n, int64_t units, int64_t nbytes, int64_t divisor);
+// The caller's host ids on the current device for the length of one host call (freed by the
+// destructor): they cross once per call, not once per chunk.
+class HostMixedIds {
+public:
+    HostMixedIds(const uint8_t *host_ids, int64_t nstripes);
+    ~HostMixedIds();
+    HostMixedIds(const HostMixedIds &) = delete;
+    HostMixedIds &operator=(const HostMixedIds &) = delete;
+    const uint8_t *get() const { return dev_; }
+
+private:
+    uint8_t *dev_ = nullptr;
+};
 
 }  // namespace ecx
