@@ -319,6 +319,30 @@ int ecx_rs_decode_partial_batch(ecx_rs *rs, const uint8_t *shard_present, int sh
                                 int64_t in_stripe_stride, uint8_t *acc, int64_t acc_stripe_stride,
                                 int64_t acc_row_stride, int64_t nstripes, int64_t byte_count, int is_first,
                                 void *stream);
+/* Batched ReedSolomon.decodeMissingSingle (ReedSolomon.java:288-333) with a pattern and a helper
+ * shard index per stripe: the hop of the pipelined chain (ClayCodeNode.kt:165-193) for a store
+ * whose placement rotates, so that both the stripe's missing shards and the shard this helper
+ * holds change from stripe to stripe.  pattern_of_stripe and shard_of_stripe are DEVICE byte
+ * arrays of nstripes.  For stripe s with p = pattern_of_stripe[s] and i = shard_of_stripe[s] the
+ * input is in + s * in_stripe_stride + i * in_shard_stride (in_shard_stride 0: the helper's own
+ * shards back to back; non-zero: shard i of a full stripe), and acc[s][o] (=, or ^= unless
+ * is_first) D_p[o][i] * input for o over pattern p's missing shards in ascending order -- bit for
+ * bit what ecx_rs_decode_partial_batch(rs, pattern p, i, ...) gives for that stripe: data and
+ * parity rows, the first-k rule, zero from a shard pattern p does not read.  Rows at or past
+ * pattern p's missing count are untouched; a stripe whose id has no pattern, whose pattern misses
+ * nothing, or whose shard byte is >= n is untouched entirely, also with is_first.  Whatever the two
+ * arrays hold, nothing outside the plan and the stripe's own input is read.  in and acc must not
+ * overlap.  Only enqueues; the first use of a set on a device uploads its partial-sum plan
+ * (npatterns * n * 192 bytes) and must happen outside stream capture (refused under capture,
+ * nothing enqueued).  Checked in this order: null set ECX_E_NULL; negative nstripes or byte_count
+ * ECX_E_ILLEGAL_ARGUMENT; nstripes == 0, byte_count == 0 or a set whose patterns miss nothing
+ * ECX_OK (no buffers, no device); a null pointer among the four ECX_E_NULL; a negative stride or
+ * an extent beyond int64_t ECX_E_ILLEGAL_ARGUMENT. */
+int ecx_rs_decode_partial_batch_mixed(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                      const uint8_t *shard_of_stripe, const uint8_t *in, int64_t in_stripe_stride,
+                                      int64_t in_shard_stride, uint8_t *acc, int64_t acc_stripe_stride,
+                                      int64_t acc_row_stride, int64_t nstripes, int64_t byte_count, int is_first,
+                                      void *stream);
 /* Batched ReedSolomon.encodeParitySingle (ReedSolomon.java:110-118; LRC chains,
  * NodeHelper.kt:89): acc[s][p] (=, or ^= unless is_first) parityRows[p][input_index] * in[s]
  * for every parity row p. */

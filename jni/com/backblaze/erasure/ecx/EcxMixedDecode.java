@@ -106,6 +106,26 @@ public final class EcxMixedDecode {
                 blockBytes));
     }
 
+    /**
+     * One hop of the pipelined repair chain (ReedSolomon.decodeMissingSingle,
+     * ReedSolomon.java:288-333, for every missing shard) with a pattern and a helper shard index per
+     * stripe: for stripe s, shard shardOfStripe[s] -- read at
+     * in + s * inStripeStride + shardOfStripe[s] * inShardStride; inShardStride 0 = this helper's own
+     * shards back to back -- adds its contribution to every shard that pattern patternOfStripe[s]
+     * misses: acc + s * accStripeStride + o * accRowStride is assigned when isFirst, XOR-accumulated
+     * otherwise, for o over the pattern's missing shards in ascending order.  Both arrays are device
+     * byte arrays of nstripes.  Rows past a pattern's missing count, and stripes whose id names no
+     * pattern, whose pattern misses nothing or whose shard byte is no shard, are left untouched.
+     * in and acc must not overlap.  Only enqueues on {@code stream}; the first hop on a device must
+     * run outside stream capture.
+     */
+    public void decodePartialBatch(long patternOfStripe, long shardOfStripe, long in, long inStripeStride,
+                                   long inShardStride, long acc, long accStripeStride, long accRowStride,
+                                   long nstripes, long byteCount, boolean isFirst, long stream) {
+        Ecx.check(EcxNative.rsDecodePartialBatchMixed(handle(), patternOfStripe, shardOfStripe, in, inStripeStride,
+                inShardStride, acc, accStripeStride, accRowStride, nstripes, byteCount, isFirst ? 1 : 0, stream));
+    }
+
     /** {patterns, shards per stripe, most shards any pattern misses}. */
     public int[] info() {
         int[] n = new int[1], shards = new int[1], missing = new int[1];

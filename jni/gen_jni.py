@@ -152,6 +152,8 @@ RULES = {
     "ecx_rs_recommended_pitch": ((), [A("pitch", "1")]),
     "ecx_rs_decode_missing_blocked_batch": (("rs",), [A("shard_present", RS_N)]),
     "ecx_rs_decode_partial_batch": (("rs",), [A("shard_present", RS_N)]),
+    # the hop with a pattern and a shard per stripe: addresses only, as the other mixed device calls
+    "ecx_rs_decode_partial_batch_mixed": ((), [NN("nstripes", "byte_count")]),
     "ecx_clay_create": ((), [NN("n_erased"), A("erased", "n_erased")]),
     "ecx_clay_create_shortened": ((), [NN("n_erased"), A("erased", "n_erased")]),
     "ecx_clay_create_ex": ((), [NN("n_erased"), A("erased", "n_erased")]),

@@ -896,6 +896,27 @@ class ReedSolomon:
                                                 in_stripe_stride, _dev_ptr(acc), acc_stripe_stride, acc_row_stride,
                                                 nstripes, byteCount, 1 if isFirst else 0, _stream(stream)))
 
+    def decodePartialBatchMixed(self, patternSet, ids, shardOfStripe, inp, in_stripe_stride, in_shard_stride, acc,
+                                acc_stripe_stride, acc_row_stride, nstripes, byteCount, isFirst, stream=None):
+        """decodePartialBatch with a pattern and a helper shard index per stripe, in one launch
+        (ecx_rs_decode_partial_batch_mixed): stripe s adds shard ``shardOfStripe[s]``'s contribution
+        to every shard pattern ``ids[s]`` of ``patternSet`` misses; both are device uint8 arrays of
+        nstripes.  The stripe's input is ``inp + s * in_stripe_stride + shardOfStripe[s] *
+        in_shard_stride`` (in_shard_stride 0: this helper's own shards back to back).  An id without
+        a pattern, a pattern with nothing missing, or a shard byte that is no shard leaves its
+        stripe untouched; so do the rows past a pattern's missing count."""
+        self._check_pattern_set(patternSet)
+        n = self.getTotalShardCount()
+        _check_layout(inp, in_stripe_stride, in_shard_stride, n - 1 if in_shard_stride else 0, nstripes, byteCount,
+                      "input")
+        _check_layout(acc, acc_stripe_stride, acc_row_stride, patternSet.info()[2] - 1, nstripes, byteCount, "acc")
+        _check_layout(ids, 1, 0, 0, nstripes, 1, "ids")
+        _check_layout(shardOfStripe, 1, 0, 0, nstripes, 1, "shardOfStripe")
+        check(lib().ecx_rs_decode_partial_batch_mixed(patternSet._h, _dev_ptr(ids), _dev_ptr(shardOfStripe),
+                                                      _dev_ptr(inp), in_stripe_stride, in_shard_stride, _dev_ptr(acc),
+                                                      acc_stripe_stride, acc_row_stride, nstripes, byteCount,
+                                                      1 if isFirst else 0, _stream(stream)))
+
     def encodePartialBatch(self, inputIndex, inp, in_stripe_stride, acc, acc_stripe_stride, acc_row_stride,
                            nstripes, byteCount, isFirst, stream=None):
         """Batched encodeParitySingle into every parity row."""

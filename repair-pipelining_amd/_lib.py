@@ -127,6 +127,7 @@ SIGNATURES = {
     "ecx_rs_decode_missing_blocked_mixed_batch_host": (I, [P, P, P, I64, I64, I64]),
     "ecx_rs_index_patterns": (I, [I, P, I64, P, I, PI, P]),
     "ecx_rs_decode_partial_batch": (I, [P, P, I, P, I64, P, I64, I64, I64, I64, I, P]),
+    "ecx_rs_decode_partial_batch_mixed": (I, [P, P, P, P, I64, I64, P, I64, I64, I64, I64, I, P]),
     "ecx_rs_encode_partial_batch": (I, [P, I, P, I64, P, I64, I64, I64, I64, I, P]),
     "ecx_clay_create": (I, [I, I, P, I, ctypes.POINTER(P)]),
     "ecx_clay_create_shortened": (I, [I, I, I, P, I, ctypes.POINTER(P)]),

@@ -29,6 +29,11 @@ design.
 The per-rank kernels are the library's compiled maps (``GfMap``); there is no CPU
 fallback.  ``map_factory`` exists only so that CPU tests can rehearse the
 orchestration with gloo and a test-only stand-in.
+
+``RepairChain`` runs one composed map per run.  ``PatternChain`` is its twin for RS
+stripes under rotating placement, where the shards a stripe misses and the shard index
+each helper holds change per stripe: the same transport, ring and slicing, with the
+per-slice hop (``_hop``) made of ``decodePartialBatchMixed`` calls over a pattern set.
 """
 from __future__ import annotations
 
@@ -96,9 +101,7 @@ class RepairChain:
         missing = sorted(set(cols_of) - set(self.order))
         if missing:
             raise ValueError(f"ranks {missing} own inputs of the map but are not on the chain")
-        if self.dest in self.order and self.dest != self.order[-1]:
-            raise ValueError("dest must be the last rank of the chain or off the chain (the rebuilt node)")
-        self.pos = self.order.index(rank) if rank in self.order else -1
+        self._place_on_chain()
         self.map, self.n_cols = None, 0
         cols = cols_of.get(rank, []) if self.pos >= 0 else []
         if cols:
@@ -108,6 +111,26 @@ class RepairChain:
             local = [placement(int(in_slot[j]))[1] for j in cols]
             self.map = map_factory(np.ascontiguousarray(m[:, cols]), in_slot=local, out_slot=list(out_slot))
             self.n_cols = len(cols)
+
+    def _place_on_chain(self):
+        if self.dest in self.order and self.dest != self.order[-1]:
+            raise ValueError("dest must be the last rank of the chain or off the chain (the rebuilt node)")
+        self.pos = self.order.index(self.rank) if self.rank in self.order else -1
+
+    # ---------------------------------------------------------------- one slice
+    def _hop(self, local, lo, hi, acc, B):
+        """This rank's contribution to stripes [lo, hi), into the slice buffer `acc`
+        ([hi - lo][n_out_slots][B]): assigned at position 0, accumulated behind it."""
+        n, row = hi - lo, self.n_out_slots * B
+        if self.n_cols:
+            src = local[lo:hi]
+            lstride = local.shape[1] * B
+            if self.pos == 0:
+                self.map.apply_batch(src, lstride, B, acc, row, B, n, B)
+            else:
+                self.map.accumulate_batch(src, lstride, B, acc, row, B, n, B)
+        elif self.pos == 0:
+            acc.zero_()
 
     # ---------------------------------------------------------------- transport
     def _isend(self, t, dst):
@@ -139,7 +162,6 @@ class RepairChain:
         if self.pos < 0 and self.rank != self.dest:
             return
         B, S = sub_bytes, nstripes
-        row = self.n_out_slots * B
         n_slices = (S + slice_stripes - 1) // slice_stripes
         last = self.pos == len(self.order) - 1
         nxt = self.dest if last else (self.order[self.pos + 1] if self.pos >= 0 else None)
@@ -155,7 +177,6 @@ class RepairChain:
         ring = [] if deliver_here else [torch.empty((slice_stripes, self.n_out_slots, B), dtype=torch.uint8,
                                                     device=dev) for _ in range(n_buffers)]
         sends: List[Optional[object]] = [None] * max(1, n_buffers)
-        lstride = local.shape[1] * B if self.n_cols else 0
 
         def target(s, n):
             if deliver_here:
@@ -186,19 +207,83 @@ class RepairChain:
                 pending = (t1, self._irecv(t1, prev))
             else:
                 pending = None
-            if self.n_cols:
-                src = local[lo:hi]
-                if self.pos == 0:
-                    self.map.apply_batch(src, lstride, B, acc, row, B, n, B)
-                else:
-                    self.map.accumulate_batch(src, lstride, B, acc, row, B, n, B)
-            elif self.pos == 0:
-                acc.zero_()
+            self._hop(local, lo, hi, acc, B)
             if not deliver_here:
                 sends[s % n_buffers] = self._isend(acc, nxt)
         for w in sends:
             if w is not None:
                 w.wait()
+
+
+class _SetPartial:
+    """The hop of a PatternChain on the library: ReedSolomon.decodePartialBatchMixed."""
+
+    def __init__(self, rs, pattern_set):
+        self.rs, self.set = rs, pattern_set
+        self.max_missing = pattern_set.info()[2]
+
+    def __call__(self, ids, shard_of, inp, in_stripe_stride, acc, acc_stripe_stride, acc_row_stride, nstripes,
+                 byte_count, is_first):
+        self.rs.decodePartialBatchMixed(self.set, ids, shard_of, inp, in_stripe_stride, 0, acc, acc_stripe_stride,
+                                        acc_row_stride, nstripes, byte_count, is_first)
+
+
+class PatternChain(RepairChain):
+    """The pattern-set twin of RepairChain, for RS stripes under rotating placement: the shards a
+    stripe misses differ from stripe to stripe, and so does the shard index each helper holds
+    for it, so there is no one composed matrix per run.  Every rank holds ``nlocal`` node-local
+    shards per stripe; its hop is one ``decodePartialBatchMixed`` (k_gf_partial_mixed) per local
+    slot, with the stripe's pattern id and the slot's shard index read per stripe on the device.
+
+    rs, pattern_set: the code and its ``ReedSolomon.patternSet``.
+    order, dest, group: as RepairChain.  Every rank that holds shards belongs on the chain.
+    partial_factory: ``partial_factory(rs, pattern_set)`` returns the hop -- an object with
+        ``max_missing`` and ``__call__(ids, shard_of, inp, in_stripe_stride, acc, acc_stripe_stride,
+        acc_row_stride, nstripes, byte_count, is_first)``.  It exists only so that CPU tests can
+        rehearse the orchestration with gloo and a test-only stand-in; the default is the library's
+        kernel, and there is no CPU fallback.
+    """
+
+    def __init__(self, rs, pattern_set, order: Sequence[int], rank: int, dest: Optional[int] = None, group=None,
+                 partial_factory=None):
+        self.rank, self.order, self.group = rank, list(order), group
+        self.dest = self.order[-1] if dest is None else dest
+        self._place_on_chain()
+        self.partial = (partial_factory or _SetPartial)(rs, pattern_set)
+        self.n_out_slots = int(self.partial.max_missing)
+        self._ids = self._shard_of = None
+
+    def _hop(self, local, lo, hi, acc, B):
+        """Position 0 zero-fills the slice buffer, so rows past a stripe's missing count and
+        stripes without a pattern arrive as zeros; then one call per local slot, the chain's very
+        first one assigning, every other accumulating."""
+        n, row = hi - lo, self.n_out_slots * B
+        if self.pos == 0:
+            acc.zero_()
+        nlocal = 0 if local is None else local.shape[1]
+        src = local[lo:hi].reshape(-1) if nlocal else None
+        for slot in range(nlocal):
+            self.partial(self._ids[lo:hi], self._shard_of[slot, lo:hi], src[slot * B:], nlocal * B, acc, row, B, n, B,
+                         self.pos == 0 and slot == 0)
+
+    def run(self, local, shard_of, ids, nstripes: int, shard_bytes: int, out=None, slice_stripes: int = 64,
+            n_buffers: int = 3, device=None):
+        """Repair `nstripes` stripes.
+
+        local: this rank's shards, a contiguous [nstripes][nlocal][shard_bytes] uint8 tensor.
+        shard_of: a [nlocal][nstripes] uint8 tensor on local's device: the shard index local slot j
+            holds for stripe s (a byte that is no shard index: that slot sits the stripe out).
+        ids: a [nstripes] uint8 tensor on local's device: each stripe's pattern in the set.
+        out: on `dest`, a contiguous [nstripes][max_missing][shard_bytes] tensor: row o of stripe s
+            receives the o-th missing shard of its pattern (ascending); rows past a stripe's
+            missing count, and stripes whose id has no pattern, receive zeros.
+        Ranks off the chain (and not dest) return at once."""
+        self._ids, self._shard_of = ids, shard_of
+        try:
+            super().run(local, nstripes, shard_bytes, out=out, slice_stripes=slice_stripes, n_buffers=n_buffers,
+                        device=device)
+        finally:
+            self._ids = self._shard_of = None
 
 
 class _StagedRecv:

@@ -1096,6 +1096,43 @@ int ecx_rs_decode_partial_batch(ecx_rs *rs, const uint8_t *shard_present, int sh
     });
 }
 
+namespace {
+// base + (count - 1) * stride per (count, stride) pair + bytes, as the furthest byte a batch reaches
+// from its base pointer; false when a stride is negative or the sum leaves int64_t.
+bool extent_fits(std::initializer_list<std::pair<int64_t, int64_t>> dims, int64_t bytes) {
+    int64_t total = bytes;
+    for (const auto &d : dims) {
+        int64_t span = 0;
+        if (d.second < 0) return false;
+        if (__builtin_mul_overflow(d.first > 0 ? d.first - 1 : 0, d.second, &span) ||
+            __builtin_add_overflow(total, span, &total))
+            return false;
+    }
+    return true;
+}
+}  // namespace
+
+// tests/test_partial_mixed_cpu.py pins the order of the checks.
+int ecx_rs_decode_partial_batch_mixed(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                      const uint8_t *shard_of_stripe, const uint8_t *in, int64_t in_stripe_stride,
+                                      int64_t in_shard_stride, uint8_t *acc, int64_t acc_stripe_stride,
+                                      int64_t acc_row_stride, int64_t nstripes, int64_t byte_count, int is_first,
+                                      void *stream) {
+    return guarded(__func__, [&]() -> int {
+        if (!set) throw Error(ECX_E_NULL, "null pattern set");
+        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        if (nstripes == 0 || byte_count == 0 || set->max_missing == 0) return ECX_OK;
+        if (!pattern_of_stripe || !shard_of_stripe || !in || !acc) throw Error(ECX_E_NULL, "null device pointer");
+        const int n = set->rs->code.n();
+        if (!extent_fits({{nstripes, in_stripe_stride}, {n, in_shard_stride}}, byte_count) ||
+            !extent_fits({{nstripes, acc_stripe_stride}, {set->max_missing, acc_row_stride}}, byte_count))
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative stride, or the batch's extent is beyond int64_t");
+        launch_partial_mixed(*set->set, n, pattern_of_stripe, shard_of_stripe, in, in_stripe_stride, in_shard_stride, acc,
+                             acc_stripe_stride, acc_row_stride, nstripes, byte_count, is_first != 0, (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+
 int ecx_rs_encode_partial_batch(ecx_rs *rs, int input_index, const uint8_t *in, int64_t in_stripe_stride,
                                 uint8_t *acc, int64_t acc_stripe_stride, int64_t acc_row_stride, int64_t nstripes,
                                 int64_t byte_count, int is_first, void *stream) {

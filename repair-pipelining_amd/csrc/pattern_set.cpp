@@ -5,7 +5,7 @@
 
 namespace ecx {
 
-PatternSet::PatternSet(const std::vector<const CompiledMap *> &maps) {
+PatternSet::PatternSet(const std::vector<const CompiledMap *> &maps) : maps_(maps) {
     // each map's unpadded entries and tile record: its plan padded to a multiple of 1
     std::vector<HostPlan> plans;
     plans.reserve(maps.size());
@@ -45,6 +45,55 @@ PatternSet::~PatternSet() {
         (void)hipFree(kv.second.tiles);
         (void)hipSetDevice(cur);
     }
+    for (auto &kv : partial_dev_) {
+        int cur = 0;
+        if (hipGetDevice(&cur) != hipSuccess) continue;
+        (void)hipSetDevice(kv.first);
+        (void)hipFree(kv.second.entries);
+        (void)hipFree(kv.second.rows);
+        (void)hipSetDevice(cur);
+    }
+}
+
+const PartialPlan &PatternSet::partial_plan(int n) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (partial_.npatterns != 0) {
+        if (partial_.n != n) throw Error(ECX_E_ILLEGAL_ARGUMENT, "the pattern set's partial plan is of another code");
+        return partial_;
+    }
+    std::vector<PartialPatternIn> in;
+    for (const CompiledMap *m : maps_) {
+        const LinearMap &lm = m->map();
+        in.push_back(PartialPatternIn{lm.n_out, lm.n_in, lm.a.data(), lm.in_slot.data()});
+    }
+    if (!build_partial_plan(in.data(), (int)in.size(), n, &partial_))
+        throw Error(ECX_E_ILLEGAL_ARGUMENT, "a pattern set's partial plan takes patterns of at most " +
+                                                std::to_string(kPartialRows) + " missing shards");
+    return partial_;
+}
+
+const PartialDevicePlan &PatternSet::partial_plan_for_current_device(int n) {
+    const PartialPlan &hp = partial_plan(n);
+    int dev = 0;
+    check_hip(hipGetDevice(&dev), "hipGetDevice");
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = partial_dev_.find(dev);
+    if (it != partial_dev_.end()) return it->second;
+    refuse_if_capturing("the pattern set's partial-sum plan");
+    PartialDevicePlan p;
+    auto upload = [](uint32_t **dst, const std::vector<uint32_t> &src, const char *what) {
+        check_hip(hipMalloc(dst, src.size() * 4), what);
+        check_hip(hipMemcpy(*dst, src.data(), src.size() * 4, hipMemcpyHostToDevice), "partial plan upload");
+    };
+    try {
+        upload(&p.entries, hp.entries, "hipMalloc(partial plan entries)");
+        upload(&p.rows, hp.rows, "hipMalloc(partial plan rows)");
+    } catch (...) {  // a half-uploaded plan is never published
+        (void)hipFree(p.entries);
+        (void)hipFree(p.rows);
+        throw;
+    }
+    return partial_dev_.emplace(dev, p).first->second;
 }
 
 const MixedDevicePlan &PatternSet::plan_for_current_device(int depth) {

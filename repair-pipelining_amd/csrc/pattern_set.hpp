@@ -7,6 +7,7 @@
 #include "blocked_layout.hpp"
 #include "engine.hpp"
 #include "mixed_plan.hpp"
+#include "partial_plan.hpp"
 
 namespace ecx {
 
@@ -14,13 +15,22 @@ namespace ecx {
 static_assert(kMixedEntryDwords == kEntryDwords && kMixedTileDwords == kTileDwords && kMixedTileRows == kTileRows &&
                   kMixedDummySlot == kDummySlot,
               "mixed_plan.hpp and engine.hpp describe one plan format");
+static_assert(kPartialEntryDwords == kEntryDwords && kPartialRows == kTileRows && kPartialRecords == kMixedRecords,
+              "partial_plan.hpp and engine.hpp describe one plan format");
 
 struct MixedDevicePlan {
     uint32_t *entries = nullptr;
     uint32_t *tiles = nullptr;  // kMixedRecords records
 };
 
-// The maps are only read while the set is built.
+struct PartialDevicePlan {
+    uint32_t *entries = nullptr;  // npatterns * n entries
+    uint32_t *rows = nullptr;     // kPartialRecords row counts
+};
+
+// The maps are read while the set is built, and once more when its partial-sum plan is (the first
+// ecx_rs_decode_partial_batch_mixed with the set): they must live as long as the set does.  The
+// codec a set holds a reference on keeps them.
 class PatternSet {
 public:
     // Throws ECX_E_ILLEGAL_ARGUMENT for an empty list, more than kMixedRecords maps or a map of
@@ -43,8 +53,16 @@ public:
     // The plan uploaded for the current device, lazily, like CompiledMap::plan_for_current_device.
     // A first-use site: refused on a capturing stream (engine.hpp refuse_if_capturing).
     const MixedDevicePlan &plan_for_current_device(int depth);
+    // The partial-sum plan (partial_plan.hpp) for a code of n shards, built on the first call --
+    // creating a set costs nothing for it -- and its upload for the current device, lazily, a
+    // first-use site like plan_for_current_device.
+    const PartialPlan &partial_plan(int n);
+    const PartialDevicePlan &partial_plan_for_current_device(int n);
 
 private:
+    std::vector<const CompiledMap *> maps_;
+    PartialPlan partial_;  // npatterns == 0: not built yet
+    std::map<int, PartialDevicePlan> partial_dev_;  // by device
     MixedPlan plan4_, plan8_;
     int preferred_depth_ = 4;
     std::vector<int> up_slots_, down_slots_;
@@ -71,6 +89,13 @@ void launch_apply_mixed_units(PatternSet &set, const uint8_t *ids, uint8_t *base
 // caller stripes.
 void launch_apply_mixed_blocked(PatternSet &set, const uint8_t *ids, uint8_t *base, const BlockedPlan &plan,
                                 hipStream_t stream);
+
+// One hop of the partial-sum chain with a pattern and a helper shard per stripe
+// (apply_partial_mixed.hip k_gf_partial_mixed; ecx.h ecx_rs_decode_partial_batch_mixed has the
+// meaning): `ids` and `shards` are device byte arrays of nstripes, n the code's shard count.
+void launch_partial_mixed(PatternSet &set, int n, const uint8_t *ids, const uint8_t *shards, const uint8_t *in,
+                          int64_t in_stripe_stride, int64_t in_shard_stride, uint8_t *acc, int64_t acc_stripe_stride,
+                          int64_t acc_row_stride, int64_t nstripes, int64_t nbytes, bool is_first, hipStream_t stream);
 
 // The mixed decode over HOST memory (host_pipe.cpp), synchronous, in place, on the current
 // device: one pass of `units` units of n slots of nbytes bytes (stripe_stride / slot_stride apart
