@@ -8,7 +8,9 @@
 //     odd offsets equal a dense table-row application, and bytes outside the range are untouched;
 //   * outputs aliasing inputs (x ^= c * y, decodeMissing in place) give the pre-update result,
 //     and so do outputs overlapping an input at a shifted address;
-//   * host_exec_all_zero is true exactly when every output row is zero over the range.
+//   * host_exec_all_zero is true exactly when every output row is zero over the range: at lengths
+//     around every vector width and the 4 KiB block, each byte of the range flipped in turn by one
+//     bit, in every check row and in a data input, makes it false; a flip outside the range does not.
 // Exit status 0 = all good.
 #include <cstdio>
 #include <cstring>
@@ -104,6 +106,56 @@ void check_level(int level) {
             expect(host_exec_all_zero(chk, ins.data(), off, len), "check map of a valid result is all zero", level);
             buf[(size_t)(n_in + n_out - 1)][(size_t)(off + len - 1)] ^= 0x10;
             expect(!host_exec_all_zero(chk, ins.data(), off, len), "one flipped byte makes it non-zero", level);
+        }
+    }
+    // all_zero, bit by bit: over a valid result, every byte of the range flipped in turn by a single
+    // bit (bit b % 8 at byte b) -- in every check row and in one data input -- makes it false;
+    // restored it is true again, and a flip one byte before or behind the range leaves it true.
+    // Lengths 1, 63..65 (the vector widths) and 4095..4097 (host_exec.cpp's 4 KiB block).
+    for (int64_t len : {1, 63, 64, 65, 4095, 4096, 4097}) {
+        const int n_in = 3, n_out = 2;
+        const int64_t off = 3, pad = 2;
+        LinearMap chk;  // [M | I] over (inputs, outputs); every coefficient of M general (>= 2)
+        chk.n_out = n_out;
+        chk.n_in = n_in + n_out;
+        chk.a.assign((size_t)chk.n_out * chk.n_in, 0);
+        for (int o = 0; o < n_out; ++o) {
+            for (int j = 0; j < n_in; ++j) chk.a[(size_t)o * chk.n_in + j] = (uint8_t)(2 + rng() % 254);
+            chk.a[(size_t)o * chk.n_in + n_in + o] = 1;
+            chk.out_slot.push_back(o);
+        }
+        for (int j = 0; j < chk.n_in; ++j) chk.in_slot.push_back(j);
+        std::vector<std::vector<uint8_t>> buf((size_t)(n_in + n_out), std::vector<uint8_t>((size_t)(off + len + pad)));
+        for (auto &b : buf)
+            for (auto &v : b) v = (uint8_t)rng();
+        for (int o = 0; o < n_out; ++o)
+            for (int64_t i = 0; i < len; ++i) {
+                uint8_t v = 0;
+                for (int j = 0; j < n_in; ++j) v ^= f.mul(chk.at(o, j), buf[(size_t)j][(size_t)(off + i)]);
+                buf[(size_t)(n_in + o)][(size_t)(off + i)] = v;
+            }
+        std::vector<const uint8_t *> ins;
+        for (auto &b : buf) ins.push_back(b.data());
+        expect(host_exec_all_zero(chk, ins.data(), off, len), "bit sweep: the valid result is all zero", level);
+        std::vector<int> rows;  // the check rows' buffers, and one data input
+        for (int o = 0; o < n_out; ++o) rows.push_back(n_in + o);
+        rows.push_back((int)(len % n_in));
+        for (int row : rows) {
+            uint8_t *p = buf[(size_t)row].data();
+            int64_t missed = 0;
+            for (int64_t b = 0; b < len; ++b) {
+                p[off + b] ^= (uint8_t)(1u << (b % 8));
+                if (host_exec_all_zero(chk, ins.data(), off, len)) ++missed;
+                p[off + b] ^= (uint8_t)(1u << (b % 8));
+            }
+            if (missed) std::fprintf(stderr, "len %lld buffer %d: %lld single-bit flips not seen\n", (long long)len, row, (long long)missed);
+            expect(missed == 0, "bit sweep: every single flipped bit of the range makes it non-zero", level);
+            expect(host_exec_all_zero(chk, ins.data(), off, len), "bit sweep: restored, all zero again", level);
+            for (int64_t b : {off - 1, off + len}) {
+                p[b] ^= (uint8_t)(1u << (b % 8));
+                expect(host_exec_all_zero(chk, ins.data(), off, len), "bit sweep: a flip one byte outside the range passes", level);
+                p[b] ^= (uint8_t)(1u << (b % 8));
+            }
         }
     }
     // the one-coefficient form (encodeParitySingle / code_single), assign and accumulate
