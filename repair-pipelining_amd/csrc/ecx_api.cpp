@@ -728,7 +728,7 @@ int rs_apply_blocked(const char *fn, ecx_rs *rs, bool decode, const uint8_t *sha
             if (!to.multi) return ECX_OK;
             nstripes = 0;  // but the device list is still checked
         }
-        if (to.multi) for_device_ranges(to.devices, to.ndev, 0, [](int64_t, int64_t) {});  // even for an empty batch
+        if (to.multi) check_device_list(to.devices, to.ndev);  // even for an empty batch
         BlockedPlan plan;
         blocked_plan_or_throw(n, nstripes, byte_count, block, &plan);
         for (int i = 0; i < plan.count; ++i) {
@@ -1558,7 +1558,7 @@ int rs_check_blocked_host(const char *fn, ecx_rs *rs, const uint8_t *base, int64
         if (nstripes > 0 && (!base || !verdict)) throw Error(ECX_E_NULL, "null host pointer");
         BlockedPlan plan;
         blocked_plan_or_throw(n, nstripes, byte_count, block, &plan);
-        if (multi) for_device_ranges(devices, ndev, 0, [](int64_t, int64_t) {});  // the list, even for an empty batch
+        if (multi) check_device_list(devices, ndev);  // even for an empty batch
         if (nstripes == 0) return ECX_OK;
         CompiledMap &cm = rs_check_map(rs)->cm;
         auto check = [&](const BlockedPass &p, uint8_t *v) {

@@ -1,39 +1,54 @@
-// host_pipe.hpp -- the read-only host-memory batches of host_pipe.cpp (the check; the
-// map batches are declared with the engine, engine.hpp).
+// host_pipe.hpp -- the host-memory batches of host_pipe.cpp: the read-only check and the in-place
+// mixed decode, each over one device or a device list, and the plan report of the map batches.
+// host_plan.hpp has what they decide; this is what they enqueue.  The map batches themselves
+// (run_host_batch, run_host_batch_devices) are declared in engine.hpp, which this includes:
+// engine.hpp is hashed with the kernel sources of the committed PMC profile
+// (profiles/pmc_traffic.json), so its text moves only together with a new profile.
 #pragma once
 
-#include <functional>
-
 #include "engine.hpp"
+#include "host_plan.hpp"
 
 namespace ecx {
+
+class PatternSet;
+
+// How run_host_batch would move a batch (host_batch_plan over the map's used slots and the knobs).
+HostBatchPlan plan_host_batch(CompiledMap &cm, int64_t in_stripe_stride, int64_t in_slot_stride,
+                              int64_t out_stripe_stride, int64_t out_slot_stride, int64_t nstripes, int64_t nbytes);
 
 // launch_check over host-memory stripes: the check map's used slots of each chunk of stripes
 // go H2D, k_gf_check writes the chunk's verdict bytes on the device and only those come back
 // into the host array `verdict` (one byte per stripe).  Synchronous, on the current device.
 void run_host_check_batch(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_stride, int64_t in_slot_stride,
                           int64_t nstripes, int64_t nbytes, uint8_t *verdict);
-// run_host_check_batch split over a device list, as run_host_batch_devices (engine.hpp).
+// run_host_check_batch split over a device list, as run_host_batch_devices.
 void run_host_check_batch_devices(CompiledMap &cm, const uint8_t *in, int64_t in_stripe_stride,
                                   int64_t in_slot_stride, int64_t nstripes, int64_t nbytes, uint8_t *verdict,
                                   const int *devices, int ndev);
 
-// How run_host_batch moves a batch (ecx_map_host_plan, include/ecx_tune.h): stripes per chunk, the
-// chunk count, device buffer sets in flight, and per chunk the H2D / D2H copies, the most rows per
-// stripe one copy moves (> 1 where runs are folded or copied in 3D) and how many copies are 3D.
-struct HostBatchPlan {
-    int64_t chunk = 0, nchunks = 0;
-    int buffers = 0;
-    int64_t h2d_copies = 0, h2d_rows = 0, d2h_copies = 0, d2h_rows = 0, h2d_3d = 0, d2h_3d = 0;
-    int64_t slices = 0;  // column slices of a one-chunk batch (1: whole slots)
-};
-HostBatchPlan plan_host_batch(CompiledMap &cm, int64_t in_stripe_stride, int64_t in_slot_stride,
-                              int64_t out_stripe_stride, int64_t out_slot_stride, int64_t nstripes, int64_t nbytes);
+// The mixed decode over HOST memory, synchronous, in place, on the current device: one pass of
+// `units` units of n slots of nbytes bytes (stripe_stride / slot_stride apart in host memory),
+// `divisor` units per caller stripe; `dev_ids` is the device copy of the caller's ids.  Chunks of
+// units go H2D (up_slots), through launch_apply_mixed_units, and D2H (down_slots).
+void run_host_mixed_batch(PatternSet &set, const uint8_t *dev_ids, uint8_t *base, int64_t stripe_stride,
+                          int64_t slot_stride, int n, int64_t units, int64_t nbytes, int64_t divisor);
+// The caller's host ids on the current device for the length of one host call (freed by the
+// destructor): they cross once per call, not once per chunk.
+class HostMixedIds {
+public:
+    HostMixedIds(const uint8_t *host_ids, int64_t nstripes);
+    ~HostMixedIds();
+    HostMixedIds(const HostMixedIds &) = delete;
+    HostMixedIds &operator=(const HostMixedIds &) = delete;
+    const uint8_t *get() const { return dev_; }
 
-// range(lo, count) over contiguous stripe ranges of nstripes split over a device list, one worker
-// thread per entry with that device current: the split, validation and error reporting of
-// run_host_batch_devices, for host batches made of several passes (the blocked RS layout).
-void for_device_ranges(const int *devices, int ndev, int64_t nstripes,
-                       const std::function<void(int64_t, int64_t)> &range);
+private:
+    uint8_t *dev_ = nullptr;
+};
+
+// The refusals of a device list, before anything is copied: a null list, an empty one, an id that
+// is not among the visible devices.
+void check_device_list(const int *devices, int ndev);
 
 }  // namespace ecx

@@ -97,24 +97,4 @@ void launch_partial_mixed(PatternSet &set, int n, const uint8_t *ids, const uint
                           int64_t in_stripe_stride, int64_t in_shard_stride, uint8_t *acc, int64_t acc_stripe_stride,
                           int64_t acc_row_stride, int64_t nstripes, int64_t nbytes, bool is_first, hipStream_t stream);
 
-// The mixed decode over HOST memory (host_pipe.cpp), synchronous, in place, on the current
-// device: one pass of `units` units of n slots of nbytes bytes (stripe_stride / slot_stride apart
-// in host memory), `divisor` units per caller stripe; `dev_ids` is the device copy of the caller's
-// ids.  Chunks of units go H2D (up_slots), through launch_apply_mixed_units, and D2H (down_slots).
-void run_host_mixed_batch(PatternSet &set, const uint8_t *dev_ids, uint8_t *base, int64_t stripe_stride,
-                          int64_t slot_stride, int n, int64_t units, int64_t nbytes, int64_t divisor);
-// The caller's host ids on the current device for the length of one host call (freed by the
-// destructor): they cross once per call, not once per chunk.
-class HostMixedIds {
-public:
-    HostMixedIds(const uint8_t *host_ids, int64_t nstripes);
-    ~HostMixedIds();
-    HostMixedIds(const HostMixedIds &) = delete;
-    HostMixedIds &operator=(const HostMixedIds &) = delete;
-    const uint8_t *get() const { return dev_; }
-
-private:
-    uint8_t *dev_ = nullptr;
-};
-
 }  // namespace ecx

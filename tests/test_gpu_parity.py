@@ -683,7 +683,7 @@ def test_partial_sum_batches(ecx, torch_dev):
 @pytest.fixture
 def small_host_chunks(ecx):
     """Force many pipelined chunks and ring reuse (one stripe per chunk on these layouts, even with
-    the many-run rule of host_pipe.cpp); restore the defaults afterwards."""
+    the many-run rule of host_plan.cpp chunking_of); restore the defaults afterwards."""
     ecx.tune("host_chunk_kib", 16)
     ecx.tune("host_buffers", 3)
     yield
@@ -2697,7 +2697,7 @@ def test_every_entry_kind_at_once(ecx, torch_dev):
 
 @pytest.mark.parametrize("small", [False, True])
 def test_host_batch_folded_runs_match_device_batch(ecx, torch_dev, small):
-    """Host batches whose used slots repeat with a fixed step (host_pipe.cpp fold_runs: one strided
+    """Host batches whose used slots repeat with a fixed step (host_plan.cpp plan_copies: one strided
     copy of count x stripes rows per run of the first period) -- shortened Clay(10,4) single-node
     repairs of nodes in each of the four y-groups (periods of 2 to 8 runs a plane group), the
     Clay(4,2) two-node repair {0, 3} and a Clay(4,2) repair on a padded sub-chunk pitch -- write
@@ -2882,6 +2882,55 @@ def test_host_check_batch_random_layouts(ecx):
             assert verdict.tolist() == want, (case, k, m, L, off, win, pitch, S)
     finally:
         ecx.tune("host_chunk_kib", 65536)
+
+
+@pytest.fixture
+def ring_of_two_sets(ecx):
+    """One stripe per chunk over two buffer sets: 7 stripes of RS(4,2) with 4 KiB shards wrap the
+    ring of host_pipe.cpp three times, every set reused while its earlier unit may be in flight."""
+    ecx.tune("host_chunk_kib", 16)
+    ecx.tune("host_buffers", 2)
+    yield
+    ecx.tune("host_chunk_kib", 65536)
+    ecx.tune("host_buffers", 3)
+
+
+def _rs42_codewords(seed):
+    k, m, L, S = 4, 2, 4096, 7
+    host = np.random.default_rng(seed).integers(0, 256, (S, k + m, L), dtype=np.uint8)
+    for s in range(S):
+        O.ReedSolomon(k, m).encode_parity([host[s, i] for i in range(k + m)], 0, L)
+    return host
+
+
+def test_host_batch_wraps_a_ring_of_two_sets(ecx, ring_of_two_sets):
+    """The map batch through the wrapped ring: an in-place decode with shards 1 and 4 missing
+    equals the oracle's decodeMissing on every stripe."""
+    k, m, L, S = 4, 2, 4096, 7
+    host = _rs42_codewords(501)
+    present = [i not in (1, 4) for i in range(k + m)]
+    host[:, (1, 4)] = 0x5A
+    want = host.copy()
+    for s in range(S):
+        shards = [want[s, i].copy() for i in range(k + m)]
+        O.ReedSolomon(k, m).decode_missing(shards, present, 0, L)
+        want[s] = shards
+    dmap = ecx.ReedSolomon.create(k, m).decode_map(present)
+    plan = dmap.host_plan(6 * L, L, 6 * L, L, S, L)
+    assert (plan["chunk"], plan["chunks"], plan["buffers"]) == (1, 7, 2)
+    dmap.apply_batch_host(host, 6 * L, L, host, 6 * L, L, S, L)
+    assert (host == want).all()
+
+
+def test_host_check_wraps_a_ring_of_two_sets(ecx, ring_of_two_sets):
+    """The check through the wrapped ring (24 KiB up per stripe, one verdict byte back): one
+    flipped byte in a parity shard of stripe 5 fails that stripe and no other."""
+    k, m, L, S = 4, 2, 4096, 7
+    host = _rs42_codewords(502)
+    host[5, 4, 1234] ^= 0x10
+    verdict = np.full(S, 7, np.uint8)
+    ecx.ReedSolomon.create(k, m).isParityCorrectBatchHost(host, 6 * L, L, S, 0, L, verdict)
+    assert verdict.tolist() == [1, 1, 1, 1, 1, 0, 1]
 
 
 def _recorder():

@@ -1,4 +1,4 @@
-"""The host-memory batch plan (host_pipe.cpp make_plan, exported as ecx_map_host_plan; host-only,
+"""The host-memory batch plan (host_plan.cpp make_plan, exported as ecx_map_host_plan; host-only,
 no device): how a host batch is chunked and how many copies each chunk takes -- the 160-stripe
 floor for many-run layouts, periodic runs folded into one 2D copy per period, and other
 progressions of equal runs moved by one 3D copy each.  The GPU side (tests/test_gpu_parity.py::

@@ -137,6 +137,31 @@ def test_union_of_output_shards_is_uploaded_natural(ecx, kib):
     _assert_trap(host, before, want, ids)
 
 
+def test_host_mixed_decode_wraps_a_ring_of_two_sets(ecx):
+    """RS(4,2), 4 KiB shards, 16 KiB chunks over host_buffers 2: all six shards go up (24 KiB a
+    stripe), so each of the 7 stripes is a chunk and the ring of two sets wraps three times, a set
+    loaded again while its earlier stripe may still be on its way back.  Seven different one- and
+    two-shard patterns; shards 0, 1, 2, 4, 5 come back for every stripe and shard 3 for none:
+    every byte equals the oracle's."""
+    k, m, L = 4, 2, 4096
+    pats = np.ones((7, 6), np.uint8)
+    for p, missing in enumerate([(0,), (1,), (5,), (0, 2), (2, 5), (4, 5), (1, 4)]):
+        pats[p, list(missing)] = 0
+    ids = [4, 0, 6, 2, 5, 1, 3]
+    before = np.random.default_rng(9400).integers(0, 256, (len(ids), 6, L), dtype=np.uint8)
+    want = decode_by_oracle(k, m, before, pats, ids, 0, L)
+    host = before.copy()
+    rs = ecx.ReedSolomon.create(k, m)
+    buffers = ecx.tune_value("host_buffers")
+    ecx.tune("host_buffers", 2)
+    try:
+        with rs.patternSet(pats) as ps, chunk_kib(ecx, 16):
+            rs.decodeMissingBatchMixedHost(host, ps, np.array(ids, np.uint8), 6 * L, L, len(ids), 0, L)
+    finally:
+        ecx.tune("host_buffers", buffers)
+    _assert_natural(host, before, want, pats, ids)
+
+
 @pytest.mark.parametrize("kib", CHUNKS)
 def test_union_of_output_shards_is_uploaded_blocked(ecx, kib):
     """The same in the blocked layout, from pinned memory (HostBuffer): 2 KiB blocks, two per
