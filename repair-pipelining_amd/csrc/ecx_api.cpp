@@ -7,17 +7,16 @@
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
-#include <list>
-#include <map>
 #include <memory>
-#include <unordered_map>
 #include <mutex>
 #include <string>
 #include <tuple>
 
+#include "api_maps.hpp"
 #include "blocked_layout.hpp"
 #include "check_blocked.hpp"
 #include "clay_rtc.hpp"
+#include "codec_cache.hpp"
 #include "map_rtc.hpp"
 #include "engine.hpp"
 #include "host_pipe.hpp"
@@ -33,13 +32,25 @@ struct ecx_map {
     CompiledMap cm;
 };
 
+// What one of a codec's maps was built for.
+struct MapKey {
+    enum What { encode, check, decode, decode_partial, encode_partial, coding, helper_plane };
+    MapKey(What w, const std::vector<bool> &p = {}, int i = -1, int h = -1)
+        : what(w), present(p.begin(), p.end()), index(i), helper(h) {}
+    What what;
+    std::vector<uint8_t> present;  // the pattern of a decode / coding map (bytes: compared at once)
+    int index;                     // *_partial: the one input shard; helper_plane: the erased node
+    int helper;                    // helper_plane: which
+    bool operator<(const MapKey &o) const {
+        return std::tie(what, present, index, helper) < std::tie(o.what, o.present, o.index, o.helper);
+    }
+};
+using MapMemo = Memo<MapKey, ecx_map>;  // plans live as long as the codec
+
 struct ecx_rs {
     explicit ecx_rs(int k, int m) : code(k, m) {}
     RsCode code;
-    bool shared = false;  // owned by the process-wide codec registry (ecx_rs_create)
-    std::mutex mu;
-    std::unique_ptr<ecx_map> enc, check;
-    std::map<std::string, std::unique_ptr<ecx_map>> dec, partial;  // plans live as long as the codec
+    MapMemo maps;
 };
 
 // A pattern set (ecx.h): the decode maps of its patterns as one device plan.  `rs` is a reference
@@ -53,9 +64,8 @@ struct ecx_rs_pattern_set {
 struct ecx_clay {
     ecx_clay(int k, int m, std::vector<int> e, int v = 0, bool is_test = false) : pl(k, m, std::move(e), v, is_test) {}
     ClayPlanner pl;
-    bool shared = false;  // owned by the process-wide codec registry (ecx_clay_create)
-    std::mutex mu;
-    std::map<std::string, std::unique_ptr<ecx_map>> maps;
+    MapMemo maps;
+    std::mutex mu;  // of the rtc state
     // Single-node repair as the per-helper-plane kernel (clay_rtc.hpp), built on first use.
     std::unique_ptr<ClayRtc> rtc;
     int rtc_state = 0;  // 0 = not tried, 1 = available, -1 = not representable
@@ -122,13 +132,6 @@ int guarded(const char *name, F &&f) {
     }
 }
 
-std::string key_of(const std::vector<bool> &v, int extra = 0) {
-    std::string s(v.size() + 8, '\0');
-    for (size_t i = 0; i < v.size(); ++i) s[i] = v[i] ? '1' : '0';
-    std::memcpy(&s[v.size()], &extra, sizeof(int));
-    return s;
-}
-
 // ReedSolomon.checkBuffersAndSizes, ReedSolomon.java:338-363.
 void check_buffers(const RsCode &c, uint8_t *const *shards, int shard_count, int shard_length, int offset,
                    int byte_count) {
@@ -142,16 +145,6 @@ void check_buffers(const RsCode &c, uint8_t *const *shards, int shard_count, int
         throw Error(ECX_E_ILLEGAL_ARGUMENT, "buffers to small: " + std::to_string(byte_count) + std::to_string(offset));
 }
 
-LinearMap dense_map(const uint8_t *m, int n_out, int n_in) {
-    LinearMap lm;
-    lm.n_out = n_out;
-    lm.n_in = n_in;
-    lm.a.assign(m, m + (size_t)n_out * n_in);
-    for (int j = 0; j < n_in; ++j) lm.in_slot.push_back(j);
-    for (int o = 0; o < n_out; ++o) lm.out_slot.push_back(o);
-    return lm;
-}
-
 // The CodingLoop entry points receive their matrix with every call: the reference
 // passes the codec's parity rows or decode rows each time (ReedSolomon.java:105-107,
 // :262-264).  Compiling a plan costs the planner, a device upload and, when the plan
@@ -159,75 +152,22 @@ LinearMap dense_map(const uint8_t *m, int n_out, int n_in) {
 // map's content (least recently used first out; ecx_tune "plan_cache" sets the size,
 // 0 compiles every call).
 std::shared_ptr<CompiledMap> cached_plan(LinearMap lm) {
+    static LruCache<std::string, CompiledMap> plans;
     const size_t cap = (size_t)tuning().plan_cache;
-    if (cap == 0) return std::make_shared<CompiledMap>(std::move(lm));
-    std::string key(sizeof(int) * (2 + lm.in_slot.size() + lm.out_slot.size()) + lm.a.size(), '\0');
-    char *k = &key[0];
-    std::memcpy(k, &lm.n_out, sizeof(int));
-    std::memcpy(k + sizeof(int), &lm.n_in, sizeof(int));
-    k += 2 * sizeof(int);
-    std::memcpy(k, lm.in_slot.data(), lm.in_slot.size() * sizeof(int));
-    k += lm.in_slot.size() * sizeof(int);
-    std::memcpy(k, lm.out_slot.data(), lm.out_slot.size() * sizeof(int));
-    k += lm.out_slot.size() * sizeof(int);
-    std::memcpy(k, lm.a.data(), lm.a.size());
-    using Entry = std::pair<std::string, std::shared_ptr<CompiledMap>>;
-    static std::mutex mu;
-    static std::list<Entry> lru;  // front = most recently used
-    static std::unordered_map<std::string, std::list<Entry>::iterator> index;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = index.find(key);
-        if (it != index.end()) {
-            lru.splice(lru.begin(), lru, it->second);
-            return it->second->second;
-        }
-    }
-    auto plan = std::make_shared<CompiledMap>(std::move(lm));  // compiled outside the lock
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = index.find(key);
-    if (it != index.end()) return it->second->second;  // another thread compiled it first
-    lru.emplace_front(key, plan);
-    index[key] = lru.begin();
-    while (lru.size() > cap) {
-        index.erase(lru.back().first);
-        lru.pop_back();  // the plan is freed when its last in-flight user drops it
-    }
-    return plan;
-}
-
-std::vector<bool> present_vec(const uint8_t *p, int n) {
-    std::vector<bool> v(n);
-    for (int i = 0; i < n; ++i) v[i] = p[i] != 0;
-    return v;
+    auto compile = [&] { return std::make_shared<CompiledMap>(std::move(lm)); };
+    return cap == 0 ? compile() : plans.get(map_key(lm), cap, compile);  // (no cache, no key to build)
 }
 
 ecx_map *rs_decode_map(ecx_rs *rs, const std::vector<bool> &present) {
-    std::lock_guard<std::mutex> lk(rs->mu);
-    auto &slot = rs->dec[key_of(present)];
-    if (!slot) slot = std::make_unique<ecx_map>(rs->code.decode_map(present));
-    return slot.get();
+    return rs->maps.get({MapKey::decode, present}, [&] { return rs->code.decode_map(present); });
 }
 
-// isParityCorrect's map (ReedSolomon.java:129-178): row p = parityRows[p] over the data
-// shards plus 1 x parity shard p, i.e. the syndrome, all zero exactly when the parity is right.
-ecx_map *rs_check_map(ecx_rs *rs) {
-    const RsCode &c = rs->code;
-    std::lock_guard<std::mutex> lk(rs->mu);
-    if (!rs->check) {
-        LinearMap lm;
-        lm.n_out = c.m();
-        lm.n_in = c.n();
-        lm.a.assign((size_t)c.m() * c.n(), 0);
-        for (int p = 0; p < c.m(); ++p) {
-            std::memcpy(&lm.a[(size_t)p * c.n()], c.parity_row(p), (size_t)c.k());
-            lm.a[(size_t)p * c.n() + c.k() + p] = 1;
-            lm.out_slot.push_back(p);
-        }
-        for (int j = 0; j < c.n(); ++j) lm.in_slot.push_back(j);
-        rs->check = std::make_unique<ecx_map>(lm.pruned());
-    }
-    return rs->check.get();
+ecx_map *rs_check_plan(ecx_rs *rs) {
+    return rs->maps.get({MapKey::check}, [&] { return rs_check_map(rs->code); });
+}
+
+ecx_map *clay_coding_map(ecx_clay *c, const std::vector<bool> &present) {
+    return c->maps.get({MapKey::coding, present}, [&] { return c->pl.perform_coding_map(present); });
 }
 
 ecx_map *clay_standard_map(ecx_clay *c) {
@@ -236,109 +176,26 @@ ecx_map *clay_standard_map(ecx_clay *c) {
     for (int z = 0; z < a; ++z)
         for (int e : c->pl.erased())
             if (e >= 0 && e < n) present[(size_t)z * n + e] = false;
-    std::lock_guard<std::mutex> lk(c->mu);
-    auto &slot = c->maps[key_of(present, -1)];
-    if (!slot) slot = std::make_unique<ecx_map>(c->pl.perform_coding_map(present));
-    return slot.get();
+    return clay_coding_map(c, present);
 }
 
-}  // namespace
-
-namespace {
-// Process-wide codec registry: equal codecs are one reference-counted object.
-// ecx_*_create takes a reference, ecx_*_destroy drops it.  A codec nobody references
-// stays registered, idle, so that the next create of the same codec (the reference builds
-// one per file or repair) finds its compiled plans and generated kernels; at most
-// kCodecIdleMax idle codecs are kept, least recently released first out, and an evicted
-// codec frees its device state.  Past kCodecRegistryMax registered codecs, creates return
-// private objects that destroy frees at once.
+// Process-wide codec registries (codec_cache.hpp RefRegistry): equal codecs are one
+// reference-counted object.  ecx_*_create takes a reference, ecx_*_destroy drops it.  A codec
+// nobody references stays registered, idle, so that the next create of the same codec (the
+// reference builds one per file or repair) finds its compiled plans and generated kernels; at most
+// kCodecIdleMax idle codecs are kept, and an evicted codec frees its device state.  Past
+// kCodecRegistryMax registered codecs, creates return private objects that destroy frees at once.
 constexpr size_t kCodecRegistryMax = 4096;
 constexpr size_t kCodecIdleMax = 64;
 
-template <typename T, typename Key>
-struct Registry {
-    std::mutex mu;
-    std::map<Key, std::unique_ptr<T>> reg;
-    std::map<const T *, Key> key_of;
-    std::list<const T *> idle;  // front = most recently released
-    std::map<const T *, typename std::list<const T *>::iterator> idle_pos;
-    std::map<const T *, int> refs;
-    std::map<const T *, std::unique_ptr<T>> priv;  // private objects (registry full): freed by destroy
-
-    template <typename Make>
-    T *get(const Key &key, Make make) {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = reg.find(key);
-        if (it != reg.end()) {
-            T *obj = it->second.get();
-            auto ip = idle_pos.find(obj);
-            if (ip != idle_pos.end()) {
-                idle.erase(ip->second);
-                idle_pos.erase(ip);
-            }
-            ++refs[obj];
-            return obj;
-        }
-        std::unique_ptr<T> obj(make());  // may throw (invalid geometry): nothing registered
-        if (reg.size() >= kCodecRegistryMax) {
-            T *p = obj.get();
-            priv.emplace(p, std::move(obj));
-            return p;
-        }
-        obj->shared = true;
-        T *p = obj.get();
-        reg.emplace(key, std::move(obj));
-        key_of.emplace(p, key);
-        refs[p] = 1;
-        return p;
-    }
-
-    // Drops one reference; frees a private object, parks a shared one as idle.  A pointer
-    // the registry does not hold a live reference for (a second destroy) is ignored, never
-    // dereferenced.
-    void release(T *obj) {
-        if (!obj) return;
-        std::vector<std::unique_ptr<T>> evicted;  // destroyed outside the lock (hipFree syncs)
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            auto pv = priv.find(obj);
-            if (pv != priv.end()) {
-                evicted.push_back(std::move(pv->second));
-                priv.erase(pv);
-                return;
-            }
-            auto r = refs.find(obj);
-            if (r == refs.end() || r->second <= 0) return;  // not a live reference: ignore
-            if (--r->second > 0) return;
-            idle.push_front(obj);
-            idle_pos[obj] = idle.begin();
-            while (idle.size() > kCodecIdleMax) {
-                const T *victim = idle.back();
-                idle.pop_back();
-                idle_pos.erase(victim);
-                refs.erase(victim);
-                auto k = key_of.find(victim);
-                auto e = reg.find(k->second);
-                evicted.push_back(std::move(e->second));
-                reg.erase(e);
-                key_of.erase(k);
-            }
-        }
-    }
-
-    void stats(int *live, int *idle_n) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (live) *live = (int)(reg.size() - idle.size());
-        if (idle_n) *idle_n = (int)idle.size();
-    }
-};
-
-Registry<ecx_rs, std::pair<int, int>> &rs_registry() {
-    static Registry<ecx_rs, std::pair<int, int>> r;
+using RsRegistry = RefRegistry<ecx_rs, std::pair<int, int>>;
+RsRegistry &rs_registry() {
+    static RsRegistry r(kCodecRegistryMax, kCodecIdleMax);
     return r;
 }
-Registry<ecx_clay, std::tuple<int, int, int, std::vector<int>, int>> &clay_registry() {
-    static Registry<ecx_clay, std::tuple<int, int, int, std::vector<int>, int>> r;
+using ClayRegistry = RefRegistry<ecx_clay, std::tuple<int, int, int, std::vector<int>, int>>;
+ClayRegistry &clay_registry() {
+    static ClayRegistry r(kCodecRegistryMax, kCodecIdleMax);
     return r;
 }
 }  // namespace
@@ -452,20 +309,9 @@ int ecx_check_some_shards(const uint8_t *matrix_rows, const uint8_t *const *inpu
         if (input_count <= 0 || check_count < 0 || offset < 0 || byte_count < 0)
             throw Error(ECX_E_ILLEGAL_ARGUMENT, "invalid counts");
         // row o: sum_i M[o][i]*in[i] + 1*to_check[o] == 0  <=>  to_check[o] is correct
-        const int w = input_count + check_count;
-        LinearMap lm;
-        lm.n_out = check_count;
-        lm.n_in = w;
-        lm.a.assign((size_t)check_count * w, 0);
-        for (int o = 0; o < check_count; ++o) {
-            std::memcpy(&lm.a[(size_t)o * w], matrix_rows + (size_t)o * input_count, (size_t)input_count);
-            lm.a[(size_t)o * w + input_count + o] = 1;
-            lm.out_slot.push_back(o);
-        }
-        for (int j = 0; j < w; ++j) lm.in_slot.push_back(j);
         std::vector<const uint8_t *> ptrs(inputs, inputs + input_count);
         ptrs.insert(ptrs.end(), to_check, to_check + check_count);
-        const std::shared_ptr<CompiledMap> cm = cached_plan(lm.pruned());
+        const std::shared_ptr<CompiledMap> cm = cached_plan(check_map(matrix_rows, check_count, input_count));
         return run_host_all_zero(*cm, ptrs.data(), offset, byte_count) ? 1 : 0;
     });
 }
@@ -481,8 +327,7 @@ int ecx_code_single(const uint8_t *matrix_rows, int row_length, const uint8_t *i
             host_exec_scale(c, input + offset, output + offset, byte_count, !is_first_time);
             return ECX_OK;
         }
-        const uint8_t row[2] = {c, (uint8_t)(is_first_time ? 0 : 1)};
-        const std::shared_ptr<CompiledMap> cm = cached_plan(dense_map(row, 1, 2));
+        const std::shared_ptr<CompiledMap> cm = cached_plan(scale_map(c, !is_first_time));
         const uint8_t *ins[2] = {input, output};
         uint8_t *outs[1] = {output};
         run_host(*cm, ins, outs, offset, byte_count);
@@ -496,7 +341,7 @@ int ecx_code_single(const uint8_t *matrix_rows, int row_length, const uint8_t *i
 // step) per file or repair (SampleEncoder.java:83, ClayCode.java:43-51), and sharing keeps
 // the compiled, device-resident plans -- and the hiprtc-compiled Clay kernels -- of every
 // earlier call instead of rebuilding them per object.  Shared codecs are reference-
-// counted; up to kCodecIdleMax unreferenced ones stay cached (Registry above).
+// counted; up to kCodecIdleMax unreferenced ones stay cached (rs_registry above).
 int ecx_rs_create(int data_shards, int parity_shards, ecx_rs **out) {
     return guarded(__func__, [&]() -> int {
         *out = nullptr;
@@ -523,9 +368,7 @@ int ecx_rs_shape(const ecx_rs *rs, int *data_shards, int *parity_shards) {
 
 int ecx_rs_encode_map(ecx_rs *rs, const ecx_map **out) {
     return guarded(__func__, [&]() -> int {
-        std::lock_guard<std::mutex> lk(rs->mu);
-        if (!rs->enc) rs->enc = std::make_unique<ecx_map>(rs->code.encode_map());
-        *out = rs->enc.get();
+        *out = rs->maps.get({MapKey::encode}, [&] { return rs->code.encode_map(); });
         return ECX_OK;
     });
 }
@@ -533,8 +376,7 @@ int ecx_rs_encode_map(ecx_rs *rs, const ecx_map **out) {
 int ecx_rs_decode_map(ecx_rs *rs, const uint8_t *shard_present, const ecx_map **out) {
     return guarded(__func__, [&]() -> int {
         std::vector<bool> present = present_vec(shard_present, rs->code.n());
-        int np = 0;
-        for (bool b : present) np += b;
+        const int np = (int)std::count(present.begin(), present.end(), true);
         if (np < rs->code.k()) throw Error(ECX_E_NOT_ENOUGH_SHARDS, "Not enough shards present");
         *out = rs_decode_map(rs, present);
         return ECX_OK;
@@ -647,36 +489,12 @@ int ecx_rs_index_patterns(int shards, const uint8_t *present, int64_t nstripes, 
         if (shards <= 0 || nstripes < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
         if (cap < 1 || cap > kMixedRecords)
             throw Error(ECX_E_ILLEGAL_ARGUMENT, "cap is outside 1..256: " + std::to_string(cap));
-        std::map<std::string, int> index;
-        std::string row((size_t)shards, '\0');
-        for (int64_t s = 0; s < nstripes; ++s) {
-            for (int i = 0; i < shards; ++i) row[(size_t)i] = present[(size_t)s * shards + i] ? 1 : 0;
-            auto it = index.find(row);
-            if (it == index.end()) {
-                if ((int)index.size() == cap)
-                    throw Error(ECX_E_ILLEGAL_ARGUMENT, "more than " + std::to_string(cap) + " distinct patterns");
-                std::memcpy(patterns + index.size() * (size_t)shards, row.data(), (size_t)shards);
-                it = index.emplace(row, (int)index.size()).first;
-            }
-            ids[s] = (uint8_t)it->second;
-        }
-        *npatterns = (int)index.size();
+        *npatterns = index_patterns(shards, present, nstripes, patterns, cap, ids);
         return ECX_OK;
     });
 }
 
 namespace {
-// The plain layout's pitch (scripts/rs_layout_contract.py): the smallest
-// ODD multiple of 4 KiB at or above the shard.  4 KiB-aligned shards run full-chunk kernels only,
-// and an odd count keeps the streams off the power-of-two boundaries whose address bits the HBM
-// interleave does not spread (section 4, "Where the streams collide": 4 MiB + 4 KiB, not 4 MiB).
-int64_t recommended_pitch(int64_t byte_count) {
-    constexpr int64_t kStep = 4 << 10;
-    int64_t c = (byte_count + kStep - 1) / kStep;
-    if (c % 2 == 0 && c > 0) ++c;
-    return c * kStep;
-}
-
 // The blocked layout's block and its passes are blocked_layout.hpp's (no HIP header there: the
 // plan is tested on the CPU); here its refusals become status codes.
 int64_t resolve_block(int n, int64_t byte_count, int64_t block_bytes) {
@@ -888,8 +706,7 @@ int ecx_rs_encode_parity_single(ecx_rs *rs, const uint8_t *shard, uint8_t *outpu
             host_exec_scale(c.parity_row(output_index)[input_index], shard + offset, output + offset, byte_count, true);
             return ECX_OK;
         }
-        const uint8_t row[2] = {c.parity_row(output_index)[input_index], 1};
-        const std::shared_ptr<CompiledMap> cm = cached_plan(dense_map(row, 1, 2));
+        const std::shared_ptr<CompiledMap> cm = cached_plan(scale_map(c.parity_row(output_index)[input_index], true));
         const uint8_t *ins[2] = {shard, output};
         uint8_t *outs[1] = {output};
         run_host(*cm, ins, outs, offset, byte_count);
@@ -903,7 +720,7 @@ int ecx_rs_is_parity_correct(ecx_rs *rs, uint8_t *const *shards, int shard_count
         check_buffers(rs->code, shards, shard_count, shard_length, first_byte, byte_count);
         if (temp_buffer && (long long)temp_length < (long long)first_byte + byte_count)
             throw Error(ECX_E_ILLEGAL_ARGUMENT, "tempBuffer is not big enough");
-        return run_host_all_zero(rs_check_map(rs)->cm, shards, first_byte, byte_count) ? 1 : 0;
+        return run_host_all_zero(rs_check_plan(rs)->cm, shards, first_byte, byte_count) ? 1 : 0;
     });
 }
 
@@ -915,7 +732,7 @@ int ecx_rs_is_parity_correct_batch(ecx_rs *rs, const uint8_t *base, int64_t stri
         if (nstripes < 0 || offset < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
         if (nstripes == 0) return ECX_OK;
         if (!base || !verdict) throw Error(ECX_E_NULL, "null device pointer");
-        launch_check(rs_check_map(rs)->cm, base + offset, stripe_stride, shard_stride, verdict, nstripes, byte_count,
+        launch_check(rs_check_plan(rs)->cm, base + offset, stripe_stride, shard_stride, verdict, nstripes, byte_count,
                      (hipStream_t)stream);
         return ECX_OK;
     });
@@ -926,8 +743,7 @@ int ecx_rs_decode_missing(ecx_rs *rs, uint8_t *const *shards, const uint8_t *sha
     return guarded(__func__, [&]() -> int {
         check_buffers(rs->code, shards, shard_count, shard_length, offset, byte_count);
         std::vector<bool> present = present_vec(shard_present, rs->code.n());
-        int np = 0;
-        for (bool b : present) np += b;
+        const int np = (int)std::count(present.begin(), present.end(), true);
         if (np == rs->code.n()) return ECX_OK;
         if (np < rs->code.k()) throw Error(ECX_E_NOT_ENOUGH_SHARDS, "Not enough shards present");
         ecx_map *m = rs_decode_map(rs, present);
@@ -942,35 +758,13 @@ int ecx_rs_decode_missing_single(ecx_rs *rs, const uint8_t *shard, int shard_ind
     (void)shard_index;
     return guarded(__func__, [&]() -> int {
         const RsCode &c = rs->code;
-        std::vector<bool> present = present_vec(shard_present, c.n());
-        int np = 0;
-        for (bool b : present) np += b;
-        // fewer than k present leaves zero rows in the sub-matrix: "Matrix is singular"
-        if (np < c.k()) throw Error(ECX_E_SINGULAR, "Matrix is singular");
-        const Matrix dec = c.data_decoder(present, nullptr);
-        std::vector<int> missing;
-        for (int i = 0; i < c.k(); ++i)
-            if (!present[i]) missing.push_back(i);
-        if (output_count > c.m() || (int)missing.size() > c.m()) throw Error(ECX_E_INDEX, "matrixRows index");
-        if (output_count > (int)missing.size()) throw Error(ECX_E_NULL, "no decode row for this output (no missing data shard)");
-        if (index < 0 || index >= c.k()) throw Error(ECX_E_INDEX, "matrix column index");
+        // row j: out_j (=|^=) D^-1[missing_j][index] * shard; its refusals come first
+        LinearMap lm = decode_single_map(c, present_vec(shard_present, c.n()), index, output_count, is_first != 0);
         if (offset < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "invalid counts");
-        if (output_count == 0) return ECX_OK;
-        // row j: out_j (=|^=) D^-1[missing_j][index] * shard
-        const int w = 1 + output_count;
-        LinearMap lm;
-        lm.n_out = output_count;
-        lm.n_in = w;
-        lm.a.assign((size_t)output_count * w, 0);
-        for (int j = 0; j < output_count; ++j) {
-            lm.a[(size_t)j * w] = dec.at(missing[j], index);
-            if (!is_first) lm.a[(size_t)j * w + 1 + j] = 1;
-            lm.out_slot.push_back(j);
-        }
-        for (int j = 0; j < w; ++j) lm.in_slot.push_back(j);
+        if (lm.n_out == 0) return ECX_OK;
         std::vector<const uint8_t *> ins(1, shard);
         ins.insert(ins.end(), outputs, outputs + output_count);
-        const std::shared_ptr<CompiledMap> cm = cached_plan(lm.pruned());
+        const std::shared_ptr<CompiledMap> cm = cached_plan(std::move(lm));
         run_host(*cm, ins.data(), outputs, offset, byte_count);
         return ECX_OK;
     });
@@ -1050,22 +844,6 @@ int ecx_map_accumulate_batch(const ecx_map *map, const uint8_t *in, int64_t in_s
 }
 
 // ---------------------------------------------------------------- batched partial sums
-namespace {
-// One-input map: row o = coefficient of `column` in row o of `m` (0 if absent).
-ecx_map *single_input_map(const LinearMap &m, int column_slot, std::vector<int> out_slots) {
-    LinearMap lm;
-    lm.n_in = 1;
-    lm.in_slot.push_back(0);
-    lm.n_out = m.n_out;
-    lm.out_slot = std::move(out_slots);
-    int col = -1;
-    for (int j = 0; j < m.n_in; ++j)
-        if (m.in_slot[j] == column_slot) col = j;
-    for (int o = 0; o < m.n_out; ++o) lm.a.push_back(col < 0 ? 0 : m.at(o, col));
-    return new ecx_map(lm);
-}
-}  // namespace
-
 int ecx_rs_decode_partial_batch(ecx_rs *rs, const uint8_t *shard_present, int shard_index, const uint8_t *in,
                                 int64_t in_stripe_stride, uint8_t *acc, int64_t acc_stripe_stride,
                                 int64_t acc_row_stride, int64_t nstripes, int64_t byte_count, int is_first,
@@ -1074,43 +852,17 @@ int ecx_rs_decode_partial_batch(ecx_rs *rs, const uint8_t *shard_present, int sh
         const RsCode &c = rs->code;
         if (shard_index < 0 || shard_index >= c.n()) throw Error(ECX_E_INDEX, "shard index");
         std::vector<bool> present = present_vec(shard_present, c.n());
-        int np = 0;
-        for (bool b : present) np += b;
+        const int np = (int)std::count(present.begin(), present.end(), true);
         if (np < c.k()) throw Error(ECX_E_NOT_ENOUGH_SHARDS, "Not enough shards present");
         if (np == c.n()) return ECX_OK;
         ecx_map *full = rs_decode_map(rs, present);  // rows: the missing shards, data AND parity
-        ecx_map *part;
-        {
-            std::lock_guard<std::mutex> lk(rs->mu);
-            auto &slot = rs->partial[key_of(present, shard_index)];
-            if (!slot) {
-                std::vector<int> rows;
-                for (int o = 0; o < full->cm.map().n_out; ++o) rows.push_back(o);
-                slot.reset(single_input_map(full->cm.map(), shard_index, rows));
-            }
-            part = slot.get();
-        }
+        ecx_map *part = rs->maps.get({MapKey::decode_partial, present, shard_index},
+                                     [&] { return single_input_map(full->cm.map(), shard_index); });
         launch_apply(part->cm, in, in_stripe_stride, 0, acc, acc_stripe_stride, acc_row_stride, nstripes, byte_count,
                      (hipStream_t)stream, !is_first);
         return ECX_OK;
     });
 }
-
-namespace {
-// base + (count - 1) * stride per (count, stride) pair + bytes, as the furthest byte a batch reaches
-// from its base pointer; false when a stride is negative or the sum leaves int64_t.
-bool extent_fits(std::initializer_list<std::pair<int64_t, int64_t>> dims, int64_t bytes) {
-    int64_t total = bytes;
-    for (const auto &d : dims) {
-        int64_t span = 0;
-        if (d.second < 0) return false;
-        if (__builtin_mul_overflow(d.first > 0 ? d.first - 1 : 0, d.second, &span) ||
-            __builtin_add_overflow(total, span, &total))
-            return false;
-    }
-    return true;
-}
-}  // namespace
 
 // tests/test_partial_mixed_cpu.py pins the order of the checks.
 int ecx_rs_decode_partial_batch_mixed(const ecx_rs_pattern_set *set, const uint8_t *pattern_of_stripe,
@@ -1139,23 +891,8 @@ int ecx_rs_encode_partial_batch(ecx_rs *rs, int input_index, const uint8_t *in, 
     return guarded(__func__, [&]() -> int {
         const RsCode &c = rs->code;
         if (input_index < 0 || input_index >= c.k()) throw Error(ECX_E_INDEX, "data shard index");
-        ecx_map *part;
-        {
-            std::lock_guard<std::mutex> lk(rs->mu);
-            auto &slot = rs->partial[key_of({}, -1 - input_index)];
-            if (!slot) {
-                LinearMap lm;
-                lm.n_in = 1;
-                lm.in_slot.push_back(0);
-                lm.n_out = c.m();
-                for (int p = 0; p < c.m(); ++p) {
-                    lm.a.push_back(c.parity_row(p)[input_index]);
-                    lm.out_slot.push_back(p);
-                }
-                slot = std::make_unique<ecx_map>(lm);
-            }
-            part = slot.get();
-        }
+        ecx_map *part = rs->maps.get({MapKey::encode_partial, {}, input_index},
+                                     [&] { return encode_partial_map(c, input_index); });
         launch_apply(part->cm, in, in_stripe_stride, 0, acc, acc_stripe_stride, acc_row_stride, nstripes, byte_count,
                      (hipStream_t)stream, !is_first);
         return ECX_OK;
@@ -1226,14 +963,7 @@ int ecx_clay_perform_coding(ecx_clay *clay, const uint8_t *const *inputs, uint8_
         const int w = clay->pl.n_real() * clay->pl.alpha();
         std::vector<bool> present(w);
         for (int j = 0; j < w; ++j) present[j] = inputs[j] != nullptr;
-        ecx_map *m;
-        {
-            std::lock_guard<std::mutex> lk(clay->mu);
-            auto &slot = clay->maps[key_of(present, -1)];
-            if (!slot) slot = std::make_unique<ecx_map>(clay->pl.perform_coding_map(present));
-            m = slot.get();
-        }
-        run_host(m->cm, inputs, outputs, 0, buf_size);
+        run_host(clay_coding_map(clay, present)->cm, inputs, outputs, 0, buf_size);
         return ECX_OK;
     });
 }
@@ -1246,13 +976,9 @@ int ecx_clay_decode_single_helper(ecx_clay *clay, const uint8_t *const *helper_c
         const int w = nh * clay->pl.n_real();
         std::vector<bool> present(w);
         for (int j = 0; j < w; ++j) present[j] = helper_coupled[j] != nullptr;
-        ecx_map *m;
-        {
-            std::lock_guard<std::mutex> lk(clay->mu);
-            auto &slot = clay->maps[key_of(present, helper_i * 4096 + erased_index)];
-            if (!slot) slot = std::make_unique<ecx_map>(clay->pl.decode_single_helper_map(present, helper_i, erased_index, nullptr));
-            m = slot.get();
-        }
+        ecx_map *m = clay->maps.get({MapKey::helper_plane, present, erased_index, helper_i}, [&] {
+            return clay->pl.decode_single_helper_map(present, helper_i, erased_index, nullptr);
+        });
         run_host(m->cm, helper_coupled, outputs, 0, buf_size);
         return ECX_OK;
     });
@@ -1378,38 +1104,17 @@ int ecx_map_planes_source(const ecx_map *map, int accumulate, char *buf, int len
 }
 
 // ---------------------------------------------------------------- LRC
-namespace {
-struct LrcCache {
-    std::mutex mu;
-    LrcCode code;
-    std::unique_ptr<ecx_map> enc;
-    std::map<uint32_t, std::unique_ptr<ecx_map>> dec;  // present mask -> map
-};
-LrcCache *lrc_cache() {
-    static LrcCache c;
-    return &c;
-}
-}  // namespace
-
 int ecx_lrc_map(const uint8_t *block_present, const ecx_map **out) {
     return guarded(__func__, [&]() -> int {
         if (!out) throw Error(ECX_E_NULL, "null out pointer");
-        LrcCache &c = *lrc_cache();
-        std::lock_guard<std::mutex> lk(c.mu);
+        static const LrcCode code;
+        static MapMemo maps;
         if (!block_present) {
-            if (!c.enc) c.enc = std::make_unique<ecx_map>(c.code.encode_map());
-            *out = c.enc.get();
+            *out = maps.get({MapKey::encode}, [&] { return code.encode_map(); });
             return ECX_OK;
         }
-        uint32_t mask = 0;
-        std::vector<bool> present(LrcCode::kN);
-        for (int i = 0; i < LrcCode::kN; ++i) {
-            present[i] = block_present[i] != 0;
-            mask |= present[i] ? (1u << i) : 0u;
-        }
-        auto &slot = c.dec[mask];
-        if (!slot) slot = std::make_unique<ecx_map>(c.code.decode_map(present));
-        *out = slot.get();
+        const std::vector<bool> present = present_vec(block_present, LrcCode::kN);
+        *out = maps.get({MapKey::decode, present}, [&] { return code.decode_map(present); });
         return ECX_OK;
     });
 }
@@ -1501,7 +1206,7 @@ int rs_check_host(const char *fn, ecx_rs *rs, const uint8_t *base, int64_t strip
         if (nstripes < 0 || offset < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
         if (stripe_stride < 0 || shard_stride < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative stride");
         if (nstripes > 0 && (!base || !verdict)) throw Error(ECX_E_NULL, "null host pointer");
-        CompiledMap &cm = rs_check_map(rs)->cm;
+        CompiledMap &cm = rs_check_plan(rs)->cm;
         const uint8_t *in = nstripes > 0 ? base + offset : base;
         if (multi) run_host_check_batch_devices(cm, in, stripe_stride, shard_stride, nstripes, byte_count, verdict,
                                                 devices, ndev);
@@ -1534,7 +1239,7 @@ int ecx_rs_is_parity_correct_blocked_batch(ecx_rs *rs, const uint8_t *base, int6
         const int64_t block = resolve_block(rs->code.n(), byte_count, block_bytes);
         if (nstripes == 0) return ECX_OK;
         if (!base || !verdict) throw Error(ECX_E_NULL, "null device pointer");
-        launch_check_blocked(rs_check_map(rs)->cm, base, rs->code.n(), nstripes, byte_count, block, verdict,
+        launch_check_blocked(rs_check_plan(rs)->cm, base, rs->code.n(), nstripes, byte_count, block, verdict,
                              (hipStream_t)stream);
         return ECX_OK;
     });
@@ -1560,7 +1265,7 @@ int rs_check_blocked_host(const char *fn, ecx_rs *rs, const uint8_t *base, int64
         blocked_plan_or_throw(n, nstripes, byte_count, block, &plan);
         if (multi) check_device_list(devices, ndev);  // even for an empty batch
         if (nstripes == 0) return ECX_OK;
-        CompiledMap &cm = rs_check_map(rs)->cm;
+        CompiledMap &cm = rs_check_plan(rs)->cm;
         auto check = [&](const BlockedPass &p, uint8_t *v) {
             if (multi) run_host_check_batch_devices(cm, base + p.offset, p.stripe_stride, p.slot_bytes, p.units,
                                                     p.slot_bytes, v, devices, ndev);
@@ -1579,11 +1284,7 @@ int rs_check_blocked_host(const char *fn, ecx_rs *rs, const uint8_t *base, int64
             }
             unit.assign((size_t)p.units, 0);
             check(p, unit.data());
-            for (int64_t s = 0; s < nstripes; ++s) {
-                uint8_t ok = i == 0 ? 1 : verdict[s];
-                for (int64_t j = 0; j < p.divisor; ++j) ok = (uint8_t)(ok && unit[(size_t)(s * p.divisor + j)]);
-                verdict[s] = ok;
-            }
+            fold_unit_verdicts(unit.data(), p.divisor, i == 0, verdict, nstripes);
         }
         return ECX_OK;
     });
