@@ -396,6 +396,45 @@ int ecx_clay_perform_coding_batch(ecx_clay *clay, const uint8_t *in, int64_t in_
                                   int64_t in_sub_stride, uint8_t *out, int64_t out_stripe_stride,
                                   int64_t out_sub_stride, int64_t nstripes, int64_t buf_size, void *stream);
 
+/* A Clay pattern set -- performCoding (ClayCodeErasureDecodingStep.java:53-107) over a batch whose
+ * stripes lost DIFFERENT nodes, in one launch.  The set holds up to 256 erased-node lists of one
+ * geometry as one device plan; list p is the standard-null-pattern performCoding map of
+ * ecx_clay_create_ex(data_units, parity_units, virtual_units, list p, 0): input slot z*n + node,
+ * output slot z*|E_p| + j.  `erased` holds the lists back to back, n_erased[p] entries for list p.
+ * An empty list is the "nothing erased" pattern and does nothing; duplicate lists are allowed.
+ * The set holds one codec reference per distinct list and drops them in destroy.
+ * Refused: npatterns outside 1..256 (ECX_E_ILLEGAL_ARGUMENT); a list the single step refuses (that
+ * step's own status); a list whose map has more than 64 rows (ECX_E_ILLEGAL_ARGUMENT) -- the
+ * geometries with 256 rows per node, Clay(10,4) and Clay(12,4), are left out: repair such stripes
+ * with ecx_clay_perform_coding_batch, one list per call. */
+typedef struct ecx_clay_pattern_set ecx_clay_pattern_set;
+int ecx_clay_pattern_set_create(int data_units, int parity_units, int virtual_units,
+                                const int *erased /* the lists back to back */,
+                                const int *n_erased /* npatterns counts */, int npatterns,
+                                ecx_clay_pattern_set **out);
+/* Frees the set and its device plans (ClayCodeErasureDecodingStep.java:53-107 has no counterpart:
+ * the reference builds one step per repair).  NULL is ignored. */
+void ecx_clay_pattern_set_destroy(ecx_clay_pattern_set *set);
+/* The set's list count, the step's real node count n, alpha, and the most nodes any list erases
+ * (the shape checks of ClayCodeErasureDecodingStep.java:53-107: a stripe takes n*alpha inputs
+ * and up to max_erased*alpha outputs).  Each out pointer may be NULL. */
+int ecx_clay_pattern_set_info(const ecx_clay_pattern_set *set, int *npatterns, int *nodes, int *alpha,
+                              int *max_erased);
+/* performCoding (ClayCodeErasureDecodingStep.java:53-107) with a list per stripe, in the layout of
+ * ecx_clay_perform_coding_batch: stripe s is repaired with list pattern_of_stripe[s] (a DEVICE
+ * byte array of nstripes, read by the kernel) and receives output slots 0 .. |E_p|*alpha - 1.
+ * Left untouched: the slots past that; every slot of a stripe whose id has no list or whose list is
+ * empty; every byte outside [0, buf_size) of a slot.  `in` and `out` must not overlap.  The call
+ * only enqueues.  Checked in this order: a null set (ECX_E_NULL); negative nstripes or buf_size
+ * (ECX_E_ILLEGAL_ARGUMENT); nstripes == 0, buf_size == 0 or a set whose lists are all empty
+ * (ECX_OK: no buffer is looked at, no device needed); a null pointer among the three (ECX_E_NULL);
+ * a negative stride or an extent beyond int64_t (ECX_E_ILLEGAL_ARGUMENT). */
+int ecx_clay_perform_coding_batch_mixed(const ecx_clay_pattern_set *set,
+                                        const uint8_t *pattern_of_stripe /* device */, const uint8_t *in,
+                                        int64_t in_stripe_stride, int64_t in_sub_stride, uint8_t *out,
+                                        int64_t out_stripe_stride, int64_t out_sub_stride, int64_t nstripes,
+                                        int64_t buf_size, void *stream);
+
 /* ---------------------------------------------------------------- LRC (device batch, in place) */
 /* LRCErasureCode.kt:5-9 / LRCErasureUtil.kt:3-6: K=12 data blocks in local groups of
  * R=3, one RS(3,1) parity each (parity row [1,1,1], i.e. XOR), N=16 blocks in the
@@ -447,6 +486,30 @@ int ecx_clay_perform_coding_batch_host_devices(ecx_clay *clay, const uint8_t *in
                                                int64_t in_sub_stride, uint8_t *out, int64_t out_stripe_stride,
                                                int64_t out_sub_stride, int64_t nstripes, int64_t buf_size,
                                                const int *devices, int ndev);
+/* ecx_clay_perform_coding_batch_mixed (performCoding, ClayCodeErasureDecodingStep.java:53-107,
+ * with a list per stripe) over HOST memory: `pattern_of_stripe`, `in` and `out` are host pointers.
+ * Synchronous, on the current device.  The ids cross once; chunks of stripes then go H2D (the union
+ * of the lists' input slots), through the mixed launch and D2H.  The pipeline cannot know a
+ * stripe's list, so output slots 0 .. max_p |E_p|*alpha - 1 come back for EVERY stripe, and the part
+ * a stripe's own list does not write comes back as ZEROS: the slots past |E_p|*alpha, and all of
+ * them for a stripe whose id has no list or whose list is empty.  This is the one place where the
+ * host form differs from the device form, which leaves those bytes untouched.  Host bytes outside
+ * the returned slots and outside [0, buf_size) of a slot are untouched.  The checks and their
+ * order are the device form's.  There is no _host_devices form. */
+int ecx_clay_perform_coding_mixed_batch_host(const ecx_clay_pattern_set *set,
+                                             const uint8_t *pattern_of_stripe /* host */, const uint8_t *in,
+                                             int64_t in_stripe_stride, int64_t in_sub_stride, uint8_t *out,
+                                             int64_t out_stripe_stride, int64_t out_sub_stride,
+                                             int64_t nstripes, int64_t buf_size);
+/* How ecx_clay_perform_coding_mixed_batch_host would move this batch of performCoding calls
+ * (ClayCodeErasureDecodingStep.java:53-107; host-only, no device touched): plan[7] = {input slots
+ * that go up per stripe (the union of the lists' input slots), output slots that come back per
+ * stripe (0 .. max |E|*alpha - 1), stripes per pipelined chunk, chunks, device buffer sets in
+ * flight, H2D copies per chunk, D2H copies per chunk}.  All zero when the batch moves nothing (no
+ * stripes, no bytes, a set whose lists are all empty). */
+int ecx_clay_pattern_set_host_plan(const ecx_clay_pattern_set *set, int64_t in_stripe_stride,
+                                   int64_t in_sub_stride, int64_t out_stripe_stride, int64_t out_sub_stride,
+                                   int64_t nstripes, int64_t buf_size, int64_t *plan);
 /* ReedSolomon.isParityCorrect (ReedSolomon.java:129-178) over nstripes HOST-memory stripes
  * (the layout of ecx_rs_is_parity_correct_batch, host pointers): each chunk of stripes goes
  * H2D and through the read-only check kernel, and only the verdict bytes come back --

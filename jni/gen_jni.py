@@ -8,7 +8,8 @@ export's parameters (the checks in tests/test_jni.py parse both files).  Java-si
 types:
 
   int / int64_t / uint64_t          int / long / long
-  handle (ecx_rs*, ecx_clay*, ecx_map*, ecx_rs_pattern_set*), void* stream / host or device address
+  handle (ecx_rs*, ecx_clay*, ecx_map*, ecx_rs_pattern_set*, ecx_clay_pattern_set*), void* stream /
+  host or device address
                                     long
   ecx_X **out, void **out           long[] (element 0 receives the handle / address)
   host byte buffer (uint8_t *)      byte[] (pinned with GetPrimitiveArrayCritical; may be null
@@ -54,7 +55,7 @@ HEADER = ROOT / "include" / "ecx.h"
 OUT_C = ROOT / "jni" / "ecx_jni.c"
 OUT_JAVA = ROOT / "jni" / "com" / "backblaze" / "erasure" / "ecx" / "EcxNative.java"
 JCLASS = "com_backblaze_erasure_ecx_EcxNative"
-HANDLES = ("ecx_rs", "ecx_clay", "ecx_map", "ecx_rs_pattern_set")
+HANDLES = ("ecx_rs", "ecx_clay", "ecx_map", "ecx_rs_pattern_set", "ecx_clay_pattern_set")
 # byte pointers of these functions may be NULL (C side: "NULL = ..." or unused)
 NULLABLE = {("ecx_check_some_shards", "temp_buffer"), ("ecx_rs_is_parity_correct", "temp_buffer"),
             ("ecx_lrc_map", "block_present"), ("ecx_map_create", "in_slot"), ("ecx_map_create", "out_slot"),
@@ -66,6 +67,8 @@ NULLABLE = {("ecx_check_some_shards", "temp_buffer"), ("ecx_rs_is_parity_correct
             ("ecx_rs_shape", "data_shards"), ("ecx_rs_shape", "parity_shards"),
             ("ecx_rs_pattern_set_info", "npatterns"), ("ecx_rs_pattern_set_info", "shards"),
             ("ecx_rs_pattern_set_info", "max_missing"),
+            ("ecx_clay_pattern_set_info", "npatterns"), ("ecx_clay_pattern_set_info", "nodes"),
+            ("ecx_clay_pattern_set_info", "alpha"), ("ecx_clay_pattern_set_info", "max_erased"),
             ("ecx_gf_tables", "log_table"), ("ecx_gf_tables", "exp_table"), ("ecx_gf_tables", "mul_table")}
 
 ILL, IDX = "ECX_E_ILLEGAL_ARGUMENT", "ECX_E_INDEX"
@@ -157,6 +160,17 @@ RULES = {
     "ecx_clay_create": ((), [NN("n_erased"), A("erased", "n_erased")]),
     "ecx_clay_create_shortened": ((), [NN("n_erased"), A("erased", "n_erased")]),
     "ecx_clay_create_ex": ((), [NN("n_erased"), A("erased", "n_erased")]),
+    # a Clay pattern set: npatterns counts, and the lists back to back -- as many entries as the
+    # counts add up to (int_array_sum reads them; a negative count is refused).  Both are const
+    # int[]: copied out with GetIntArrayRegion, never pinned.  Its batches take addresses only (the
+    # host form's native is package-private: "_batch_host"); their counts are refused here as the
+    # exports do.
+    "ecx_clay_pattern_set_create": ((), [NN("npatterns"), A("n_erased", "npatterns"),
+                                         A("erased", "int_array_sum(env, n_erased, npatterns)")]),
+    "ecx_clay_pattern_set_info": ((), [A("npatterns", "1"), A("nodes", "1"), A("alpha", "1"), A("max_erased", "1")]),
+    "ecx_clay_perform_coding_batch_mixed": ((), [NN("nstripes", "buf_size")]),
+    "ecx_clay_perform_coding_mixed_batch_host": ((), [NN("nstripes", "buf_size")]),
+    "ecx_clay_pattern_set_host_plan": ((), [NN("nstripes", "buf_size"), A("plan", "7")]),
     "ecx_clay_geometry": ((), [A("q", "1"), A("t", "1"), A("alpha", "1")]),
     "ecx_clay_shape": ((), [A("nodes", "1"), A("n_erased", "1"), A("alpha", "1")]),
     "ecx_clay_helper_planes": (("clay",), [A("out", "cl_a / (cl_q > 0 ? cl_q : 1)")]),
@@ -448,6 +462,24 @@ static int array_check(JNIEnv *env, jarray arr, int64_t need, int nullable, int 
     if (!arr) return nullable ? ECX_OK : ECX_E_NULL;
     if (need < 0) return ECX_E_ILLEGAL_ARGUMENT;
     return (int64_t)(*env)->GetArrayLength(env, arr) < need ? err : ECX_OK;
+}
+
+/* The sum of the first `count` elements of an int[] of counts (the lists of a Clay pattern set lie
+ * back to back: their total is what the list array must hold), read with GetIntArrayRegion; -1
+ * (refused as IllegalArgumentException by array_check) when one of them is negative.  The caller
+ * has checked that the array is non-null and holds `count` elements. */
+static int64_t int_array_sum(JNIEnv *env, jintArray arr, int64_t count) {
+    int64_t total = 0;
+    jint part[64];
+    for (int64_t i = 0; i < count; i += 64) {
+        const jsize n = (jsize)(count - i < 64 ? count - i : 64);
+        (*env)->GetIntArrayRegion(env, arr, (jsize)i, n, part);
+        for (jsize j = 0; j < n; ++j) {
+            if (part[j] < 0) return -1;
+            total += part[j];
+        }
+    }
+    return total;
 }
 
 static int buflist_pin(JNIEnv *env, ecx_jni_buflist *b) {

@@ -29,7 +29,7 @@ __all__ = [
     "lrc_encode", "lrc_encode_using_single", "lrc_decode", "sample_encode", "sample_decode",
     "device_count", "set_device", "fill_random", "count_mismatch", "shard_stripes",
     "ECChunk", "ECBlock", "ClayCodeHelper", "write_subchunk", "read_subchunk",
-    "PatternSet", "index_patterns",
+    "PatternSet", "index_patterns", "ClayPatternSet", "index_erased",
 ]
 
 
@@ -1156,6 +1156,109 @@ class ClayCodeErasureDecodingStep:
                                                                in_sub_stride, _host_ptr(out), out_stripe_stride,
                                                                out_sub_stride, nstripes, bufSize, arr.ctypes.data,
                                                                len(devs)))
+
+
+class ClayPatternSet:
+    """ecx_clay_pattern_set: up to 256 erased-node lists of one Clay geometry as one device plan,
+    for performCoding (ClayCodeErasureDecodingStep.java:53-107) over a batch whose stripes lost
+    different nodes.  List p is ``ClayCodeErasureDecodingStep(erasedLists[p], ...)``'s repair: input
+    slot z*n + node, output slot z*len(erasedLists[p]) + j.  An empty list does nothing.  close()
+    (idempotent) frees the set."""
+
+    def __init__(self, erasedLists, numDataUnits: int, numParityUnits: int, virtualUnits: int = 0):
+        lists = [[int(e) for e in lst] for lst in erasedLists]
+        flat = np.ascontiguousarray([e for lst in lists for e in lst] + [0], np.int32)  # never a null array
+        counts = np.ascontiguousarray([len(lst) for lst in lists] + [0], np.int32)
+        h = ctypes.c_void_p()
+        self._h = None
+        check(lib().ecx_clay_pattern_set_create(numDataUnits, numParityUnits, virtualUnits, flat.ctypes.data,
+                                                counts.ctypes.data, len(lists), ctypes.byref(h)))
+        self._h = h
+        self.erasedLists = lists
+        _, self.numTotalUnits, self.subPacketSize, self.maxErased = self.info()
+
+    def info(self):
+        """(lists, nodes per stripe, alpha, most nodes any list erases)."""
+        if self._h is None:
+            raise EcxError(-6, "the pattern set is closed")
+        v = [ctypes.c_int() for _ in range(4)]
+        check(lib().ecx_clay_pattern_set_info(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def host_plan(self, in_stripe_stride, in_sub_stride, out_stripe_stride, out_sub_stride, nstripes, bufSize):
+        """How performCodingBatchMixedHost would move this batch (ecx_clay_pattern_set_host_plan,
+        host-only): a dict of the input slots that go up and the output slots that come back per
+        stripe, the stripes per chunk, the chunk count, the buffer sets and the copies per chunk."""
+        if self._h is None:
+            raise EcxError(-6, "the pattern set is closed")
+        out = np.zeros(7, np.int64)
+        check(lib().ecx_clay_pattern_set_host_plan(self._h, in_stripe_stride, in_sub_stride, out_stripe_stride,
+                                                   out_sub_stride, nstripes, bufSize, out.ctypes.data))
+        keys = ("slots_up", "slots_down", "chunk", "chunks", "buffers", "h2d_copies", "d2h_copies")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def _check_batch(self, inp, iss, isl, out, oss, osl, nstripes, nbytes):
+        if self._h is None:
+            raise EcxError(-6, "the pattern set is closed")
+        if self.maxErased == 0:
+            return
+        _check_layout(inp, iss, isl, self.numTotalUnits * self.subPacketSize - 1, nstripes, nbytes, "input")
+        _check_layout(out, oss, osl, self.maxErased * self.subPacketSize - 1, nstripes, nbytes, "output")
+
+    def performCodingBatchMixed(self, inp, in_stripe_stride, in_sub_stride, out, out_stripe_stride, out_sub_stride,
+                                ids, nstripes, bufSize, stream=None) -> None:
+        """performCodingBatch with a list per stripe, in one launch
+        (ecx_clay_perform_coding_batch_mixed): stripe s is repaired with list ``ids[s]`` (a device
+        uint8 tensor of nstripes) into output slots 0 .. len(list)*alpha - 1; everything else of
+        ``out`` is left untouched.  Only enqueues."""
+        self._check_batch(inp, in_stripe_stride, in_sub_stride, out, out_stripe_stride, out_sub_stride, nstripes,
+                          bufSize)
+        _check_extent(ids, nstripes, "ids")
+        check(lib().ecx_clay_perform_coding_batch_mixed(self._h, _dev_ptr(ids), _dev_ptr(inp), in_stripe_stride,
+                                                        in_sub_stride, _dev_ptr(out), out_stripe_stride,
+                                                        out_sub_stride, nstripes, bufSize, _stream(stream)))
+
+    def performCodingBatchMixedHost(self, inp, in_stripe_stride, in_sub_stride, out, out_stripe_stride,
+                                    out_sub_stride, ids, nstripes, bufSize) -> None:
+        """performCodingBatchMixed over host memory, synchronous
+        (ecx_clay_perform_coding_mixed_batch_host).  Output slots 0 .. maxErased*alpha - 1 come back
+        for every stripe; the part a stripe's own list does not write comes back as zeros."""
+        self._check_batch(inp, in_stripe_stride, in_sub_stride, out, out_stripe_stride, out_sub_stride, nstripes,
+                          bufSize)
+        _check_extent(ids, nstripes, "ids")
+        check(lib().ecx_clay_perform_coding_mixed_batch_host(self._h, _host_ptr(ids), _host_ptr(inp),
+                                                             in_stripe_stride, in_sub_stride, _host_ptr(out),
+                                                             out_stripe_stride, out_sub_stride, nstripes, bufSize))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            lib().ecx_clay_pattern_set_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def index_erased(lists_per_stripe, cap: int = 256):
+    """(lists, ids) of per-stripe erased-node lists: the distinct lists in order of first
+    appearance (as tuples; the order of a list's nodes matters, as erasedIndexes does) and, as a
+    uint8 array, for each stripe the index of its list among them -- the inputs of ClayPatternSet
+    and, once on the device, of performCodingBatchMixed."""
+    index, ids = {}, np.zeros(len(lists_per_stripe), np.uint8)
+    for s, lst in enumerate(lists_per_stripe):
+        key = tuple(int(e) for e in lst)
+        if key not in index:
+            if len(index) >= min(cap, 256):
+                raise EcxError(-1, "more than %d distinct erased-node lists" % min(cap, 256))
+            index[key] = len(index)
+        ids[s] = index[key]
+    return list(index), ids
 
 
 class JavaRandom:

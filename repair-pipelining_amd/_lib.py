@@ -140,6 +140,10 @@ SIGNATURES = {
     "ecx_clay_decode_single_helper": (I, [P, PP, I, PP, I, I]),
     "ecx_clay_map": (I, [P, ctypes.POINTER(P)]),
     "ecx_clay_perform_coding_batch": (I, [P, P, I64, I64, P, I64, I64, I64, I64, P]),
+    "ecx_clay_pattern_set_create": (I, [I, I, I, P, P, I, ctypes.POINTER(P)]),
+    "ecx_clay_pattern_set_destroy": (None, [P]),
+    "ecx_clay_pattern_set_info": (I, [P, PI, PI, PI, PI]),
+    "ecx_clay_perform_coding_batch_mixed": (I, [P, P, P, I64, I64, P, I64, I64, I64, I64, P]),
     "ecx_lrc_map": (I, [P, ctypes.POINTER(P)]),
     "ecx_lrc_encode_batch": (I, [P, I64, I64, I64, I64, P]),
     "ecx_lrc_decode_batch": (I, [P, I64, I64, P, I64, I64, P]),
@@ -147,6 +151,8 @@ SIGNATURES = {
     "ecx_clay_perform_coding_batch_host": (I, [P, P, I64, I64, P, I64, I64, I64, I64]),
     "ecx_map_apply_batch_host_devices": (I, [P, P, I64, I64, P, I64, I64, I64, I64, P, I]),
     "ecx_clay_perform_coding_batch_host_devices": (I, [P, P, I64, I64, P, I64, I64, I64, I64, P, I]),
+    "ecx_clay_perform_coding_mixed_batch_host": (I, [P, P, P, I64, I64, P, I64, I64, I64, I64]),
+    "ecx_clay_pattern_set_host_plan": (I, [P, I64, I64, I64, I64, I64, I64, P]),
     "ecx_rs_is_parity_correct_batch_host": (I, [P, P, I64, I64, I64, I64, I64, P]),
     "ecx_rs_is_parity_correct_batch_host_devices": (I, [P, P, I64, I64, I64, I64, I64, P, P, I]),
     "ecx_host_alloc": (I, [I64, ctypes.POINTER(P)]),

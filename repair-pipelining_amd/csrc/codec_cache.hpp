@@ -1,6 +1,6 @@
 // codec_cache.hpp -- the three caches behind the C ABI (ecx_api.cpp): the
-// reference-counted registry of shared codecs, the least-recently-used cache of per-call plans,
-// and the build-once table of a codec's maps.
+// reference-counted registry of shared codecs (and the bundle of references one owner holds on
+// it), the least-recently-used cache of per-call plans, and the build-once table of a codec's maps.
 //
 // Standard library only -- no HIP header, no ABI type, no unit of the engine: what they own is a
 // template argument, so their counting, ordering and locking run -- and are tested -- on the CPU
@@ -102,6 +102,38 @@ private:
     std::map<const T *, Record> by_ptr_;  // owns the records
     KeyIndex by_key_;
     std::list<Record *> idle_;  // front = most recently released
+};
+
+// The references one owner holds on a registry's objects, one per distinct key (a Clay pattern
+// set: one codec per distinct erased-node list).  get() takes a reference the first time a key is
+// asked for and returns the same object afterwards; the destructor drops them all.
+template <typename T, typename Key>
+class RefBundle {
+public:
+    explicit RefBundle(RefRegistry<T, Key> &reg) : reg_(reg) {}
+    ~RefBundle() {
+        for (auto &kv : held_) reg_.release(kv.second);
+    }
+    RefBundle(const RefBundle &) = delete;
+    RefBundle &operator=(const RefBundle &) = delete;
+    template <typename Make>
+    T *get(const Key &key, Make make) {
+        auto it = held_.find(key);
+        if (it != held_.end()) return it->second;
+        T *obj = reg_.get(key, make);
+        try {
+            held_.emplace(key, obj);
+        } catch (...) {
+            reg_.release(obj);
+            throw;
+        }
+        return obj;
+    }
+    size_t size() const { return held_.size(); }
+
+private:
+    RefRegistry<T, Key> &reg_;
+    std::map<Key, T *> held_;
 };
 
 // Values by key, least recently used first out.  The capacity comes with each call (a knob the

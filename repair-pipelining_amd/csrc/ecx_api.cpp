@@ -198,6 +198,7 @@ ClayRegistry &clay_registry() {
     static ClayRegistry r(kCodecRegistryMax, kCodecIdleMax);
     return r;
 }
+using ClayKey = std::tuple<int, int, int, std::vector<int>, int>;
 }  // namespace
 
 const char *ecx_status_string(int s) {
@@ -1063,6 +1064,126 @@ int ecx_clay_perform_coding_batch(ecx_clay *clay, const uint8_t *in, int64_t in_
     });
 }
 
+// ---------------------------------------------------------------- Clay pattern sets
+// A Clay pattern set (ecx.h): the standard-null-pattern performCoding maps of its erased-node
+// lists as one device plan.  `codecs` holds the set's own reference on the codec of each distinct
+// list: the maps are the codecs' and live as long as they do.
+struct ecx_clay_pattern_set {
+    ecx_clay_pattern_set() : codecs(clay_registry()) {}
+    RefBundle<ecx_clay, ClayKey> codecs;
+    std::unique_ptr<PatternSet> set;  // destroyed in ~: before the references go (declared after them)
+    int npatterns = 0, nodes = 0, alpha = 0, max_erased = 0;
+};
+
+int ecx_clay_pattern_set_create(int data_units, int parity_units, int virtual_units, const int *erased,
+                                const int *n_erased, int npatterns, ecx_clay_pattern_set **out) {
+    return guarded(__func__, [&]() -> int {
+        if (out) *out = nullptr;
+        if (!out) throw Error(ECX_E_NULL, "null out pointer");
+        if (npatterns < 1 || npatterns > kMixedRecords)
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "a pattern set holds 1..256 lists: " + std::to_string(npatterns));
+        if (!n_erased) throw Error(ECX_E_NULL, "null list counts");
+        if (virtual_units < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "virtual_units");
+        int64_t total = 0;
+        for (int p = 0; p < npatterns; ++p) {
+            if (n_erased[p] < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "list " + std::to_string(p) + " has a negative count");
+            total += n_erased[p];
+        }
+        if (total > 0 && !erased) throw Error(ECX_E_NULL, "null erased lists");
+        auto set = std::make_unique<ecx_clay_pattern_set>();
+        std::vector<const CompiledMap *> maps;
+        const int *list = erased;
+        for (int p = 0; p < npatterns; list += n_erased[p], ++p) {
+            const std::vector<int> e(list, list + n_erased[p]);  // order matters (the reference's erasedIndexes)
+            // a list the single step refuses is refused with that step's status (the planner throws)
+            ecx_clay *c = set->codecs.get(std::make_tuple(data_units, parity_units, virtual_units, e, 0), [&] {
+                return new ecx_clay(data_units, parity_units, e, virtual_units, false);
+            });
+            const int rows = (int)e.size() * c->pl.alpha();
+            if (rows > kMixedMaxTiles * kTileRows) {
+                std::string names;
+                for (int x : e) names += (names.empty() ? "" : ",") + std::to_string(x);
+                throw Error(ECX_E_ILLEGAL_ARGUMENT,
+                            "list " + std::to_string(p) + " {" + names + "} has a map of " + std::to_string(rows) +
+                                " rows, a pattern set takes at most " + std::to_string(kMixedMaxTiles * kTileRows) +
+                                ": repair such stripes with ecx_clay_perform_coding_batch, one list per call");
+            }
+            maps.push_back(&clay_standard_map(c)->cm);
+            set->nodes = c->pl.n_real();
+            set->alpha = c->pl.alpha();
+            set->max_erased = std::max(set->max_erased, (int)e.size());
+        }
+        set->set = std::make_unique<PatternSet>(maps);
+        set->npatterns = npatterns;
+        *out = set.release();
+        return ECX_OK;
+    });
+}
+
+void ecx_clay_pattern_set_destroy(ecx_clay_pattern_set *set) {
+    if (!set) return;
+    set->set.reset();  // the device plans first (hipFree), then the codec references
+    delete set;
+}
+
+int ecx_clay_pattern_set_info(const ecx_clay_pattern_set *set, int *npatterns, int *nodes, int *alpha,
+                              int *max_erased) {
+    if (!set) return ECX_E_NULL;
+    if (npatterns) *npatterns = set->npatterns;
+    if (nodes) *nodes = set->nodes;
+    if (alpha) *alpha = set->alpha;
+    if (max_erased) *max_erased = set->max_erased;
+    return ECX_OK;
+}
+
+namespace {
+// The one body of the two mixed Clay batches (ecx.h); tests/test_clay_mixed_cpu.py pins the order of
+// its checks.
+int clay_mixed_batch(const char *fn, const ecx_clay_pattern_set *set, const uint8_t *pattern_of_stripe,
+                     const uint8_t *in, int64_t in_stripe_stride, int64_t in_sub_stride, uint8_t *out,
+                     int64_t out_stripe_stride, int64_t out_sub_stride, int64_t nstripes, int64_t buf_size, bool host,
+                     void *stream) {
+    return guarded(fn, [&]() -> int {
+        if (!set) throw Error(ECX_E_NULL, "null pattern set");
+        if (nstripes < 0 || buf_size < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        if (nstripes == 0 || buf_size == 0 || set->set->max_out_slot() < 0) return ECX_OK;
+        if (!pattern_of_stripe || !in || !out) throw Error(ECX_E_NULL, host ? "null host pointer" : "null device pointer");
+        const int n_in = set->nodes * set->alpha;
+        if (in_stripe_stride < 0 || in_sub_stride < 0 || out_stripe_stride < 0 || out_sub_stride < 0)
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative stride");
+        if (!extent_fits({{nstripes, in_stripe_stride}, {(int64_t)n_in, in_sub_stride}}, buf_size) ||
+            !extent_fits({{nstripes, out_stripe_stride}, {(int64_t)set->set->max_out_slot() + 1, out_sub_stride}}, buf_size))
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "batch extent overflows");
+        PatternSet &ps = *set->set;
+        if (host) {
+            const HostMixedIds ids(pattern_of_stripe, nstripes);
+            run_host_map_mixed_batch(ps, ids.get(), in, in_stripe_stride, in_sub_stride, n_in, out, out_stripe_stride,
+                                     out_sub_stride, nstripes, buf_size);
+        } else {
+            launch_map_mixed(ps, pattern_of_stripe, in, in_stripe_stride, in_sub_stride, out, out_stripe_stride,
+                             out_sub_stride, nstripes, buf_size, 0, (hipStream_t)stream);
+        }
+        return ECX_OK;
+    });
+}
+}  // namespace
+
+int ecx_clay_perform_coding_batch_mixed(const ecx_clay_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                        const uint8_t *in, int64_t in_stripe_stride, int64_t in_sub_stride,
+                                        uint8_t *out, int64_t out_stripe_stride, int64_t out_sub_stride,
+                                        int64_t nstripes, int64_t buf_size, void *stream) {
+    return clay_mixed_batch(__func__, set, pattern_of_stripe, in, in_stripe_stride, in_sub_stride, out,
+                            out_stripe_stride, out_sub_stride, nstripes, buf_size, false, stream);
+}
+
+int ecx_clay_perform_coding_mixed_batch_host(const ecx_clay_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                             const uint8_t *in, int64_t in_stripe_stride, int64_t in_sub_stride,
+                                             uint8_t *out, int64_t out_stripe_stride, int64_t out_sub_stride,
+                                             int64_t nstripes, int64_t buf_size) {
+    return clay_mixed_batch(__func__, set, pattern_of_stripe, in, in_stripe_stride, in_sub_stride, out,
+                            out_stripe_stride, out_sub_stride, nstripes, buf_size, true, nullptr);
+}
+
 int ecx_clay_rtc_compile_check(ecx_clay *clay) {
     return guarded(__func__, [&]() -> int {
         ClayRtc *r = clay_rtc(clay);
@@ -1428,6 +1549,28 @@ int ecx_map_host_plan(const ecx_map *map, int64_t in_stripe_stride, int64_t in_s
                                                  out_stripe_stride, out_slot_stride, nstripes, byte_count);
         const int64_t v[10] = {hp.chunk, hp.nchunks, hp.buffers, hp.h2d_copies, hp.h2d_rows, hp.d2h_copies,
                                hp.d2h_rows, hp.h2d_3d, hp.d2h_3d, hp.slices};
+        std::memcpy(plan, v, sizeof(v));
+        return ECX_OK;
+    });
+}
+
+int ecx_clay_pattern_set_host_plan(const ecx_clay_pattern_set *set, int64_t in_stripe_stride, int64_t in_sub_stride,
+                                   int64_t out_stripe_stride, int64_t out_sub_stride, int64_t nstripes,
+                                   int64_t buf_size, int64_t *plan) {
+    return guarded(__func__, [&]() -> int {
+        if (!set || !plan) throw Error(ECX_E_NULL, "null pattern set or plan");
+        if (nstripes < 0 || buf_size < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        int64_t v[7] = {0, 0, 0, 0, 0, 0, 0};
+        const PatternSet &ps = *set->set;
+        if (nstripes > 0 && buf_size > 0 && ps.max_out_slot() >= 0) {
+            const Tuning t = tuning();
+            const HostMapMixedPlan mp = make_map_mixed_plan(
+                ps.in_slots(), ps.out_slots(), in_stripe_stride, in_sub_stride, set->nodes * set->alpha, out_stripe_stride,
+                out_sub_stride, ps.max_out_slot() + 1, nstripes, buf_size, t.host_chunk, t.host_buffers);
+            const int64_t w[7] = {(int64_t)ps.in_slots().size(), (int64_t)ps.out_slots().size(), mp.chunk, mp.nchunks,
+                                  mp.nb, (int64_t)mp.cin.size(), (int64_t)mp.cout.size()};
+            std::memcpy(v, w, sizeof(v));
+        }
         std::memcpy(plan, v, sizeof(v));
         return ECX_OK;
     });

@@ -19,6 +19,7 @@
 // run_host_check_batch is the same ring with one verdict byte per stripe coming back, and
 // run_host_mixed_batch the same ring for a pattern set decoded in place:
 // the union of the patterns' slots goes up, the union of their output slots comes back.
+// run_host_map_mixed_batch is the ring for a pattern set run out of place.
 //
 // Everything here touches HIP; what a batch decides is host_plan.cpp.
 #include <algorithm>
@@ -358,6 +359,42 @@ void run_host_mixed_batch(PatternSet &set, const uint8_t *dev_ids, uint8_t *base
             launch_apply_mixed_units(set, dev_ids, b.in, per, nbytes, count(i), nbytes, divisor, i * chunk, s);
         },
         [&](int64_t i, HostPipe::Set &b, hipStream_t s) { copies(mp.cout, i, b, hipMemcpyDeviceToHost, s); });
+}
+
+// The out-of-place twin for a tiled set: the ring in its separate-output mode.  A set's input
+// buffer keeps every input slot of a stripe at its own index and its output buffer every output
+// slot (make_map_mixed_plan).  The launch writes only what a stripe's own pattern writes, and every
+// output slot of every stripe goes back, so the chunk's output area is cleared on the compute
+// stream first -- after the ring's wait for the earlier unit's D2H, before the launch.
+void run_host_map_mixed_batch(PatternSet &set, const uint8_t *dev_ids, const uint8_t *in, int64_t in_stripe_stride,
+                              int64_t in_slot_stride, int n_in, uint8_t *out, int64_t out_stripe_stride,
+                              int64_t out_slot_stride, int64_t nstripes, int64_t nbytes) {
+    if (nstripes <= 0 || nbytes <= 0 || set.out_slots().empty()) return;
+    const Tuning &t = tuning();
+    const int n_out = set.max_out_slot() + 1;
+    const HostMapMixedPlan mp = make_map_mixed_plan(set.in_slots(), set.out_slots(), in_stripe_stride, in_slot_stride,
+                                                    n_in, out_stripe_stride, out_slot_stride, n_out, nstripes, nbytes,
+                                                    t.host_chunk, t.host_buffers);
+    const int64_t chunk = mp.chunk;
+    auto count = [&](int64_t i) { return std::min(chunk, nstripes - i * chunk); };
+    run_ring(
+        mp.nb, mp.nchunks, (size_t)(chunk * mp.in_per), (size_t)(chunk * mp.out_per), false,
+        "hipStreamSynchronize (host map mixed batch)",
+        [&](int64_t i, HostPipe::Set &b, hipStream_t s) {
+            for (const Copy &c : mp.cin)
+                issue_copy(c, in + i * chunk * in_stripe_stride, b.in, in_stripe_stride, mp.in_per, count(i),
+                           hipMemcpyHostToDevice, s);
+        },
+        [&](int64_t i, HostPipe::Set &b, hipStream_t s) {
+            check_hip(hipMemsetAsync(b.out, 0, (size_t)(count(i) * mp.out_per), s), "hipMemsetAsync (host map mixed batch)");
+            launch_map_mixed(set, dev_ids, b.in, mp.in_per, nbytes, b.out, mp.out_per, nbytes, count(i), nbytes,
+                             i * chunk, s);
+        },
+        [&](int64_t i, HostPipe::Set &b, hipStream_t s) {
+            for (const Copy &c : mp.cout)
+                issue_copy(c, out + i * chunk * out_stripe_stride, b.out, out_stripe_stride, mp.out_per, count(i),
+                           hipMemcpyDeviceToHost, s);
+        });
 }
 
 void check_device_list(const int *devices, int ndev) {

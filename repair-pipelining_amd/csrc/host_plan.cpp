@@ -157,6 +157,27 @@ HostMixedPlan make_mixed_plan(const std::vector<int> &up, const std::vector<int>
     return mp;
 }
 
+HostMapMixedPlan make_map_mixed_plan(const std::vector<int> &ins, const std::vector<int> &outs, int64_t in_stripe_stride,
+                                     int64_t in_slot_stride, int n_in, int64_t out_stripe_stride,
+                                     int64_t out_slot_stride, int n_out, int64_t nstripes, int64_t nbytes,
+                                     int64_t host_chunk, int host_buffers) {
+    HostMapMixedPlan mp;
+    mp.in_per = (int64_t)n_in * nbytes;
+    mp.out_per = (int64_t)n_out * nbytes;
+    auto copies = [&](const std::vector<int> &slots, int64_t stripe_stride, int64_t slot_stride, int64_t per) {
+        std::vector<Run> runs = runs_of(slots, slot_stride, nbytes);
+        for (Run &r : runs) r.compact0 = r.slot0;  // not compacted
+        return plan_copies(runs, stripe_stride, slot_stride, per, nbytes);
+    };
+    mp.cin = copies(ins, in_stripe_stride, in_slot_stride, mp.in_per);
+    mp.cout = copies(outs, out_stripe_stride, out_slot_stride, mp.out_per);
+    const Chunking ch = chunking_of((int64_t)ins.size() * nbytes, mp.cin.size(), nstripes, host_chunk, host_buffers);
+    mp.chunk = ch.chunk;
+    mp.nchunks = ch.nchunks;
+    mp.nb = ch.nb;
+    return mp;
+}
+
 HostBatchPlan host_batch_plan(const std::vector<int> &ins, const std::vector<int> &outs, int64_t in_stripe_stride,
                               int64_t in_slot_stride, int64_t out_stripe_stride, int64_t out_slot_stride,
                               int64_t nstripes, int64_t nbytes, int64_t host_chunk, int host_buffers) {

@@ -81,6 +81,23 @@ HostMixedPlan make_mixed_plan(const std::vector<int> &up, const std::vector<int>
                               int64_t slot_stride, int n, int64_t units, int64_t nbytes, int64_t host_chunk,
                               int host_buffers);
 
+// The plan of a pattern set run out of place (run_host_map_mixed_batch, the Clay repair with a
+// list per stripe): a set's input buffer keeps all n_in slots of a stripe and its output buffer
+// all n_out, nbytes apart -- the set's plan addresses slots by their index -- so, as in the
+// in-place plan, the runs are not compacted.  The set's input slots go H2D; every output slot
+// comes back for every stripe (the part a stripe's own list does not write as zeros, which the
+// pipeline puts there).  Chunks are sized by the bytes that go up.
+struct HostMapMixedPlan {
+    std::vector<Copy> cin, cout;
+    int64_t in_per = 0, out_per = 0;  // a stripe on the device: [slot][nbytes], every slot
+    int64_t chunk = 1, nchunks = 0;
+    int nb = 1;
+};
+HostMapMixedPlan make_map_mixed_plan(const std::vector<int> &ins, const std::vector<int> &outs, int64_t in_stripe_stride,
+                                     int64_t in_slot_stride, int n_in, int64_t out_stripe_stride,
+                                     int64_t out_slot_stride, int n_out, int64_t nstripes, int64_t nbytes,
+                                     int64_t host_chunk, int host_buffers);
+
 // How run_host_batch moves a batch (ecx_map_host_plan, include/ecx_tune.h): stripes per chunk, the
 // chunk count, device buffer sets in flight, and per chunk the H2D / D2H copies, the most rows per
 // stripe one copy moves (> 1 where runs are folded or copied in 3D) and how many copies are 3D.

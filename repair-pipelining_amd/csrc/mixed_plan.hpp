@@ -59,4 +59,47 @@ bool build_mixed_plan(const MixedPatternIn *patterns, int npatterns, int depth, 
 // the depth, a padding entry with coefficients, entries outside the array).
 bool emulate_mixed(const MixedPlan &p, uint8_t id, const uint8_t *in, uint8_t *out, int64_t len);
 
+// ---- the tiled form (apply_map_mixed.hip k_gf_map_mixed) ----
+//
+// A set whose maps have several tiles (Clay repair of two nodes: 16 rows).  T, the tiles per
+// pattern, is the largest tile count among the set's maps, 1..kMixedMaxTiles.  The record array is
+// [kMixedRecords][T]: record (id, t) at (id * T + t) * kMixedTileDwords is tile t of pattern id;
+// every record past a pattern's own tile count and every record of an id >= npatterns is empty, so
+// every (id byte, tile < T) pair selects a record inside the plan.  The entries are those of the
+// mixed plan: each tile's padded to the depth, back to back in (pattern, tile) order, first-entry
+// indices rebased.  With T == 1 the arrays are build_mixed_plan's bit for bit.
+constexpr int kMixedMaxTiles = 8;
+
+// One pattern's map as CompiledMap holds it: `tiles` are its n_tiles tile records (kTileDwords
+// each) and `entries` the unpadded entry array they index.  Nothing else of a multi-tile map is
+// read.  n_tiles 0 is a map with no rows.
+struct TiledPatternIn {
+    const uint32_t *entries = nullptr;
+    const uint32_t *tiles = nullptr;
+    int n_tiles = 0;
+};
+
+struct TiledPlan {
+    std::vector<uint32_t> entries;  // padded, concatenated; never empty
+    std::vector<uint32_t> tiles;    // kMixedRecords * tiles_per_pattern * kMixedTileDwords
+    int npatterns = 0;
+    int tiles_per_pattern = 1;
+    int depth = 4;
+    int max_rows = 0;      // the largest row count of any tile
+    int max_out_slot = -1;  // the largest output slot of any tile
+};
+
+// mixed_depth's rule over every non-empty tile of the set.
+int tiled_depth(const TiledPatternIn *patterns, int npatterns);
+
+// Builds the tiled plan for `depth`.  False -- and *out untouched -- when npatterns is outside
+// 1..kMixedRecords, depth is not positive, a pointer is null, a pattern has more than
+// kMixedMaxTiles tiles or a tile more than kMixedTileRows rows.
+bool build_tiled_plan(const TiledPatternIn *patterns, int npatterns, int depth, TiledPlan *out);
+
+// The tiled plan applied to one stripe as k_gf_map_mixed reads it for pattern id `id` (any byte),
+// out of place: `in` is [slot][len] and is only read, `out` is [slot][len] and only the output
+// slots of the id's records are written.  False when a record breaks the plan's invariants.
+bool emulate_tiled(const TiledPlan &p, uint8_t id, const uint8_t *in, uint8_t *out, int64_t len);
+
 }  // namespace ecx

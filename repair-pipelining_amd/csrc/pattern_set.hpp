@@ -1,7 +1,9 @@
-// pattern_set.hpp -- the HIP side of a pattern set (include/ecx.h ecx_rs_pattern_set): several
-// single-tile maps of one codec compiled into one device plan (mixed_plan.hpp has the format and
-// is HIP-free), uploaded lazily per device, and the launch that decodes a batch whose stripes
-// name their pattern with one byte each (apply_mixed.hip).
+// pattern_set.hpp -- the HIP side of a pattern set (include/ecx.h ecx_rs_pattern_set,
+// ecx_clay_pattern_set): several maps of one codec compiled into one device plan (mixed_plan.hpp
+// has the formats and is HIP-free), uploaded lazily per device, and the launches that run a batch
+// whose stripes name their pattern with one byte each: in place over single-tile maps
+// (apply_mixed.hip, the RS decodes) and out of place over maps of up to kMixedMaxTiles tiles
+// (apply_map_mixed.hip, the Clay repair).
 #pragma once
 
 #include "blocked_layout.hpp"
@@ -34,7 +36,9 @@ struct PartialDevicePlan {
 class PatternSet {
 public:
     // Throws ECX_E_ILLEGAL_ARGUMENT for an empty list, more than kMixedRecords maps or a map of
-    // more than one tile.
+    // more than kMixedMaxTiles tiles.  A set with a multi-tile map has the tiled plans only: the
+    // single-tile plans of plan() stay empty (max_rows() 0), so the in-place launches do nothing
+    // with it.
     explicit PatternSet(const std::vector<const CompiledMap *> &maps);
     ~PatternSet();
     PatternSet(const PatternSet &) = delete;
@@ -44,6 +48,19 @@ public:
     int preferred_depth() const { return preferred_depth_; }
     const MixedPlan &plan(int depth) const { return depth == 8 ? plan8_ : plan4_; }
     int max_rows() const { return plan4_.max_rows; }
+    // The tiled form (mixed_plan.hpp TiledPlan; k_gf_map_mixed): tiles per pattern, the largest
+    // output slot of any pattern (-1: no pattern writes anything), the depth by tiled_depth's rule
+    // and the host plan for depth 4 or 8 (anything else is 4).
+    int tiles_per_pattern() const { return tiled4_.tiles_per_pattern; }
+    int max_out_slot() const { return tiled4_.max_out_slot; }
+    int tiled_max_rows() const { return tiled4_.max_rows; }
+    int tiled_preferred_depth() const { return tiled_depth_; }
+    const TiledPlan &tiled_plan(int depth) const { return depth == 8 ? tiled8_ : tiled4_; }
+    const MixedDevicePlan &tiled_plan_for_current_device(int depth);
+    // What an out-of-place host batch moves (host_pipe.cpp run_host_map_mixed_batch), sorted:
+    // in_slots is the union of the patterns' input slots, out_slots every slot 0..max_out_slot().
+    const std::vector<int> &in_slots() const { return in_slots_; }
+    const std::vector<int> &out_slots() const { return out_slots_; }
     // What a host batch moves (host_pipe.cpp run_host_mixed_batch), sorted: down_slots is the union
     // of the patterns' output slots, up_slots the union of every pattern's input AND output slots.
     // A stripe gets every down slot back, also one its own pattern leaves alone, so each of them
@@ -64,10 +81,12 @@ private:
     PartialPlan partial_;  // npatterns == 0: not built yet
     std::map<int, PartialDevicePlan> partial_dev_;  // by device
     MixedPlan plan4_, plan8_;
-    int preferred_depth_ = 4;
-    std::vector<int> up_slots_, down_slots_;
+    TiledPlan tiled4_, tiled8_;
+    int preferred_depth_ = 4, tiled_depth_ = 4;
+    std::vector<int> up_slots_, down_slots_, in_slots_, out_slots_;
     std::mutex mu_;
     std::map<std::pair<int, int>, MixedDevicePlan> dev_;  // (device, depth)
+    std::map<std::pair<int, int>, MixedDevicePlan> tiled_dev_;  // (device, depth)
 };
 
 // decodeMissing with a pattern per stripe, in place (apply_mixed.hip k_gf_apply_mixed): stripe s
@@ -96,5 +115,14 @@ void launch_apply_mixed_blocked(PatternSet &set, const uint8_t *ids, uint8_t *ba
 void launch_partial_mixed(PatternSet &set, int n, const uint8_t *ids, const uint8_t *shards, const uint8_t *in,
                           int64_t in_stripe_stride, int64_t in_shard_stride, uint8_t *acc, int64_t acc_stripe_stride,
                           int64_t acc_row_stride, int64_t nstripes, int64_t nbytes, bool is_first, hipStream_t stream);
+
+// A map with a pattern per stripe, out of place (apply_map_mixed.hip k_gf_map_mixed): unit u of
+// [unit][slot][bytes] at `in` is run through records (ids[first_unit + u], 0..T) of the set's
+// tiled plan over bytes [0, nbytes) of each slot, into [unit][slot][bytes] at `out`; `ids` is a
+// device byte array.  Only a record's own output slots are written; a unit whose id has no rows
+// is left untouched.  `in` and `out` must not overlap.
+void launch_map_mixed(PatternSet &set, const uint8_t *ids, const uint8_t *in, int64_t in_stripe_stride,
+                      int64_t in_slot_stride, uint8_t *out, int64_t out_stripe_stride, int64_t out_slot_stride,
+                      int64_t units, int64_t nbytes, int64_t first_unit, hipStream_t stream);
 
 }  // namespace ecx
