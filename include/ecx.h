@@ -434,6 +434,39 @@ int ecx_clay_perform_coding_batch_mixed(const ecx_clay_pattern_set *set,
                                         int64_t in_stripe_stride, int64_t in_sub_stride, uint8_t *out,
                                         int64_t out_stripe_stride, int64_t out_sub_stride, int64_t nstripes,
                                         int64_t buf_size, void *stream);
+/* One hop of the pipelined Clay repair chain (ClayCoordinator.kt:265-319 starts the chain,
+ * ClayCodeNode.kt:165-233 is a helper's step: add its share to the partial sum and forward it)
+ * with an erased-node list AND the node this helper holds per stripe: the deployment of one helper
+ * per machine under rotating placement, in one launch.  pattern_of_stripe and node_of_stripe are
+ * DEVICE byte arrays of nstripes.  For stripe s with p = pattern_of_stripe[s] and
+ * i = node_of_stripe[s], plane z of the helper's node lies at
+ * in + s * in_stripe_stride + i * in_node_stride + z * in_sub_stride (in_node_stride 0: the
+ * helper's own sub-chunks back to back, the node-major local layout; in_node_stride = sub and
+ * in_sub_stride = n * sub: node i inside a full plane-major stripe).  With M_p list p's map of
+ * ecx_clay_pattern_set_create (input slot z*n + node, output slot z*|E_p| + j), every row
+ * r in 0 .. |E_p|*alpha - 1 at acc + s * acc_stripe_stride + r * acc_sub_stride is assigned
+ * (is_first) or XORed with sum_z M_p[r][z*n + i] * in(s, z) -- bit for bit what
+ * ecx_map_accumulate_batch (ecx_map_apply_batch when is_first) gives for that stripe with the
+ * columns of node i of list p's map, so the hops of all n nodes sum to
+ * ecx_clay_perform_coding_batch_mixed.  A node list p does not read -- an erased node, or planes
+ * the single-node repair skips -- adds nothing to a running sum and assigns zeros to the list's
+ * rows with is_first.  Rows at or past |E_p|*alpha are untouched; a stripe whose id has no list,
+ * whose list is empty or whose node byte is >= n is untouched entirely, also with is_first.
+ * Whatever the two arrays hold, nothing outside the plan and the stripe's own node input is read.
+ * in and acc must not overlap.  Only enqueues; the first use of a set on a device uploads its
+ * partial-sum plan (256 * n * T tile records of 64 bytes, T the set's tiles per list, and 192
+ * bytes per ring-padded entry: 96 KiB + 22.5 KiB for the six single-node lists of Clay(4,2)) and
+ * must happen outside stream capture (refused under capture, nothing enqueued).  Checked in this
+ * order: null set ECX_E_NULL; negative nstripes or buf_size ECX_E_ILLEGAL_ARGUMENT; nstripes == 0,
+ * buf_size == 0 or a set whose lists are all empty ECX_OK (no buffers, no device); a null pointer
+ * among the four ECX_E_NULL; a negative stride or an extent beyond int64_t
+ * ECX_E_ILLEGAL_ARGUMENT. */
+int ecx_clay_partial_batch_mixed(const ecx_clay_pattern_set *set,
+                                 const uint8_t *pattern_of_stripe /* device */,
+                                 const uint8_t *node_of_stripe /* device */, const uint8_t *in,
+                                 int64_t in_stripe_stride, int64_t in_node_stride, int64_t in_sub_stride,
+                                 uint8_t *acc, int64_t acc_stripe_stride, int64_t acc_sub_stride,
+                                 int64_t nstripes, int64_t buf_size, int is_first, void *stream);
 
 /* ---------------------------------------------------------------- LRC (device batch, in place) */
 /* LRCErasureCode.kt:5-9 / LRCErasureUtil.kt:3-6: K=12 data blocks in local groups of

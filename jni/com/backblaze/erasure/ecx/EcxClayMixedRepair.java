@@ -51,6 +51,23 @@ public final class EcxClayMixedRepair {
     }
 
     /**
+     * One hop of the pipelined repair chain (ClayCoordinator.kt:265-319, ClayCodeNode.kt:165-233)
+     * with a list and a helper node per stripe: stripe s adds node nodeOfStripe[s]'s share of list
+     * patternOfStripe[s]'s repair (both device byte arrays of nstripes) to the rows at
+     * acc + s * accStripeStride + r * accSubStride, or assigns them when isFirst.  Plane z of the
+     * node lies at in + s * inStripeStride + nodeOfStripe[s] * inNodeStride + z * inSubStride
+     * (inNodeStride 0: this helper's own sub-chunks back to back).  in and acc must not overlap.
+     * Only enqueues on {@code stream} (0 = the default).
+     */
+    public void partialBatch(long patternOfStripe, long nodeOfStripe, long in, long inStripeStride, long inNodeStride,
+                             long inSubStride, long acc, long accStripeStride, long accSubStride, long nstripes,
+                             long bufSize, boolean isFirst, long stream) {
+        Ecx.check(EcxNative.clayPartialBatchMixed(handle(), patternOfStripe, nodeOfStripe, in, inStripeStride,
+                inNodeStride, inSubStride, acc, accStripeStride, accSubStride, nstripes, bufSize, isFirst ? 1 : 0,
+                stream));
+    }
+
+    /**
      * performCodingBatch over HOST-memory stripes at raw addresses, synchronous: output slots
      * 0 .. maxErased*alpha - 1 come back for every stripe, and what a stripe's own list does not
      * write comes back as zeros.  Package-private: a raw host address carries no capacity to check

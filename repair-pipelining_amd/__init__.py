@@ -1230,6 +1230,32 @@ class ClayPatternSet:
                                                              in_stripe_stride, in_sub_stride, _host_ptr(out),
                                                              out_stripe_stride, out_sub_stride, nstripes, bufSize))
 
+    def partialBatchMixed(self, ids, nodeOfStripe, inp, in_stripe_stride, in_node_stride, in_sub_stride, acc,
+                          acc_stripe_stride, acc_sub_stride, nstripes, bufSize, is_first, stream=None) -> None:
+        """One hop of the pipelined repair chain with a list and a helper node per stripe, in one
+        launch (ecx_clay_partial_batch_mixed): stripe s adds node ``nodeOfStripe[s]``'s share of list
+        ``ids[s]``'s repair to rows 0 .. len(list)*alpha - 1 of ``acc`` (assigns them when
+        ``is_first``); both are device uint8 tensors of nstripes.  Plane z of the stripe's node lies
+        at ``inp + s * in_stripe_stride + nodeOfStripe[s] * in_node_stride + z * in_sub_stride``
+        (in_node_stride 0: this helper's own sub-chunks back to back).  An id without a list, an
+        empty list or a node byte that is no node leaves its stripe untouched; so do the rows past a
+        list's own.  Only enqueues."""
+        if self._h is None:
+            raise EcxError(-6, "the pattern set is closed")
+        if self.maxErased != 0 and nstripes > 0 and bufSize > 0:
+            if in_node_stride < 0:
+                raise EcxError(-1, "input: negative stride")
+            _check_layout(inp, in_stripe_stride, in_sub_stride, self.subPacketSize - 1, nstripes,
+                          (self.numTotalUnits - 1) * in_node_stride + bufSize, "input")
+            _check_layout(acc, acc_stripe_stride, acc_sub_stride, self.maxErased * self.subPacketSize - 1, nstripes,
+                          bufSize, "acc")
+            _check_extent(ids, nstripes, "ids")
+            _check_extent(nodeOfStripe, nstripes, "nodeOfStripe")
+        check(lib().ecx_clay_partial_batch_mixed(self._h, _dev_ptr(ids), _dev_ptr(nodeOfStripe), _dev_ptr(inp),
+                                                 in_stripe_stride, in_node_stride, in_sub_stride, _dev_ptr(acc),
+                                                 acc_stripe_stride, acc_sub_stride, nstripes, bufSize,
+                                                 1 if is_first else 0, _stream(stream)))
+
     def close(self) -> None:
         if getattr(self, "_h", None) is not None:
             lib().ecx_clay_pattern_set_destroy(self._h)

@@ -144,6 +144,7 @@ SIGNATURES = {
     "ecx_clay_pattern_set_destroy": (None, [P]),
     "ecx_clay_pattern_set_info": (I, [P, PI, PI, PI, PI]),
     "ecx_clay_perform_coding_batch_mixed": (I, [P, P, P, I64, I64, P, I64, I64, I64, I64, P]),
+    "ecx_clay_partial_batch_mixed": (I, [P, P, P, P, I64, I64, I64, P, I64, I64, I64, I64, I, P]),
     "ecx_lrc_map": (I, [P, ctypes.POINTER(P)]),
     "ecx_lrc_encode_batch": (I, [P, I64, I64, I64, I64, P]),
     "ecx_lrc_decode_batch": (I, [P, I64, I64, P, I64, I64, P]),

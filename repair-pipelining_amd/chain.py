@@ -286,6 +286,79 @@ class PatternChain(RepairChain):
             self._ids = self._shard_of = None
 
 
+class _ClaySetPartial:
+    """The hop of a ClayPatternChain on the library: ClayPatternSet.partialBatchMixed."""
+
+    def __init__(self, pattern_set):
+        self.set = pattern_set
+        _, _, self.alpha, self.max_erased = pattern_set.info()
+
+    def __call__(self, ids, node_of, inp, in_stripe_stride, in_sub_stride, acc, acc_stripe_stride, acc_sub_stride,
+                 nstripes, buf_size, is_first):
+        self.set.partialBatchMixed(ids, node_of, inp, in_stripe_stride, 0, in_sub_stride, acc, acc_stripe_stride,
+                                   acc_sub_stride, nstripes, buf_size, is_first)
+
+
+class ClayPatternChain(RepairChain):
+    """The Clay twin of PatternChain, for Clay stripes under rotating placement with one helper per
+    machine: the nodes a stripe lost differ from stripe to stripe, and so does the node each
+    helper holds for it.  Every rank holds ``nlocal`` nodes per stripe, each as alpha sub-chunks
+    back to back (the node-major local layout of ``clay_node_major_placement``); its hop is one
+    ``ClayPatternSet.partialBatchMixed`` (k_gf_map_partial_mixed) per local slot, with the stripe's
+    list id and the slot's node read per stripe on the device.
+
+    pattern_set: the ``ClayPatternSet``.
+    order, dest, group: as RepairChain.  Every rank that holds nodes belongs on the chain.
+    partial_factory: ``partial_factory(pattern_set)`` returns the hop -- an object with ``alpha``,
+        ``max_erased`` and ``__call__(ids, node_of, inp, in_stripe_stride, in_sub_stride, acc,
+        acc_stripe_stride, acc_sub_stride, nstripes, buf_size, is_first)``.  It exists only so that
+        CPU tests can rehearse the orchestration with gloo and a test-only stand-in; the default is
+        the library's kernel, and there is no CPU fallback.
+    """
+
+    def __init__(self, pattern_set, order: Sequence[int], rank: int, dest: Optional[int] = None, group=None,
+                 partial_factory=None):
+        self.rank, self.order, self.group = rank, list(order), group
+        self.dest = self.order[-1] if dest is None else dest
+        self._place_on_chain()
+        self.partial = (partial_factory or _ClaySetPartial)(pattern_set)
+        self.alpha = int(self.partial.alpha)
+        self.n_out_slots = int(self.partial.max_erased) * self.alpha
+        self._ids = self._node_of = None
+
+    def _hop(self, local, lo, hi, acc, B):
+        """Position 0 zero-fills the slice buffer, so rows past a stripe's own and stripes without
+        a list arrive as zeros; then one call per local slot, the chain's very first one
+        assigning, every other accumulating."""
+        n, row = hi - lo, self.n_out_slots * B
+        if self.pos == 0:
+            acc.zero_()
+        nlocal = 0 if local is None else local.shape[1]
+        src = local[lo:hi].reshape(-1) if nlocal else None
+        for slot in range(nlocal):
+            self.partial(self._ids[lo:hi], self._node_of[slot, lo:hi], src[slot * self.alpha * B:],
+                         nlocal * self.alpha * B, B, acc, row, B, n, B, self.pos == 0 and slot == 0)
+
+    def run(self, local, node_of, ids, nstripes: int, sub_bytes: int, out=None, slice_stripes: int = 64,
+            n_buffers: int = 3, device=None):
+        """Repair `nstripes` stripes.
+
+        local: this rank's sub-chunks, a contiguous [nstripes][nlocal][alpha][sub_bytes] uint8 tensor.
+        node_of: a [nlocal][nstripes] uint8 tensor on local's device: the node local slot j holds
+            for stripe s (a byte that is no node: that slot sits the stripe out).
+        ids: a [nstripes] uint8 tensor on local's device: each stripe's list in the set.
+        out: on `dest`, a contiguous [nstripes][max_erased * alpha][sub_bytes] tensor: row
+            z * |E| + j of stripe s receives plane z of the j-th node of its list; rows past a
+            stripe's own, and stripes whose id has no list, receive zeros.
+        Ranks off the chain (and not dest) return at once."""
+        self._ids, self._node_of = ids, node_of
+        try:
+            super().run(local, nstripes, sub_bytes, out=out, slice_stripes=slice_stripes, n_buffers=n_buffers,
+                        device=device)
+        finally:
+            self._ids = self._node_of = None
+
+
 class _StagedRecv:
     """gloo rehearsal of a device-tensor irecv: host receive then copy to the device."""
 

@@ -1184,6 +1184,29 @@ int ecx_clay_perform_coding_mixed_batch_host(const ecx_clay_pattern_set *set, co
                             out_stripe_stride, out_sub_stride, nstripes, buf_size, true, nullptr);
 }
 
+// tests/test_clay_partial_mixed_cpu.py pins the order of the checks.
+int ecx_clay_partial_batch_mixed(const ecx_clay_pattern_set *set, const uint8_t *pattern_of_stripe,
+                                 const uint8_t *node_of_stripe, const uint8_t *in, int64_t in_stripe_stride,
+                                 int64_t in_node_stride, int64_t in_sub_stride, uint8_t *acc,
+                                 int64_t acc_stripe_stride, int64_t acc_sub_stride, int64_t nstripes, int64_t buf_size,
+                                 int is_first, void *stream) {
+    return guarded(__func__, [&]() -> int {
+        if (!set) throw Error(ECX_E_NULL, "null pattern set");
+        if (nstripes < 0 || buf_size < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        if (nstripes == 0 || buf_size == 0 || set->set->max_out_slot() < 0) return ECX_OK;
+        if (!pattern_of_stripe || !node_of_stripe || !in || !acc) throw Error(ECX_E_NULL, "null device pointer");
+        if (!extent_fits({{nstripes, in_stripe_stride}, {set->nodes, in_node_stride}, {set->alpha, in_sub_stride}},
+                         buf_size) ||
+            !extent_fits({{nstripes, acc_stripe_stride}, {(int64_t)set->set->max_out_slot() + 1, acc_sub_stride}},
+                         buf_size))
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative stride, or the batch's extent is beyond int64_t");
+        launch_clay_partial_mixed(*set->set, set->nodes, pattern_of_stripe, node_of_stripe, in, in_stripe_stride,
+                                  in_node_stride, in_sub_stride, acc, acc_stripe_stride, acc_sub_stride, nstripes,
+                                  buf_size, is_first != 0, (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+
 int ecx_clay_rtc_compile_check(ecx_clay *clay) {
     return guarded(__func__, [&]() -> int {
         ClayRtc *r = clay_rtc(clay);

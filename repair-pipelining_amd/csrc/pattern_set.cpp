@@ -69,6 +69,14 @@ PatternSet::~PatternSet() {
         (void)hipFree(kv.second.tiles);
         (void)hipSetDevice(cur);
     }
+    for (auto &kv : clay_partial_dev_) {
+        int cur = 0;
+        if (hipGetDevice(&cur) != hipSuccess) continue;
+        (void)hipSetDevice(kv.first.first);
+        (void)hipFree(kv.second.entries);
+        (void)hipFree(kv.second.tiles);
+        (void)hipSetDevice(cur);
+    }
     for (auto &kv : partial_dev_) {
         int cur = 0;
         if (hipGetDevice(&cur) != hipSuccess) continue;
@@ -118,6 +126,43 @@ const PartialDevicePlan &PatternSet::partial_plan_for_current_device(int n) {
         throw;
     }
     return partial_dev_.emplace(dev, p).first->second;
+}
+
+const ClayPartialPlan &PatternSet::clay_partial_plan(int n, int depth) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (clay_partial4_.npatterns == 0) {
+        ClayPartialPlan p4, p8;  // both or neither
+        if (!build_clay_partial_plan(tiled4_, n, 4, &p4) || !build_clay_partial_plan(tiled4_, n, 8, &p8))
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "a pattern set's Clay partial plan takes a code of 1..255 nodes");
+        clay_partial4_ = std::move(p4);
+        clay_partial8_ = std::move(p8);
+    }
+    if (clay_partial4_.n != n) throw Error(ECX_E_ILLEGAL_ARGUMENT, "the pattern set's partial plan is of another code");
+    return depth == 8 ? clay_partial8_ : clay_partial4_;
+}
+
+const MixedDevicePlan &PatternSet::clay_partial_plan_for_current_device(int n, int depth) {
+    const ClayPartialPlan &hp = clay_partial_plan(n, depth);
+    int dev = 0;
+    check_hip(hipGetDevice(&dev), "hipGetDevice");
+    std::lock_guard<std::mutex> lk(mu_);
+    auto it = clay_partial_dev_.find({dev, hp.depth});
+    if (it != clay_partial_dev_.end()) return it->second;
+    refuse_if_capturing("the pattern set's Clay partial-sum plan");
+    MixedDevicePlan p;
+    auto upload = [](uint32_t **dst, const std::vector<uint32_t> &src, const char *what) {
+        check_hip(hipMalloc(dst, src.size() * 4), what);
+        check_hip(hipMemcpy(*dst, src.data(), src.size() * 4, hipMemcpyHostToDevice), "Clay partial plan upload");
+    };
+    try {
+        upload(&p.entries, hp.entries, "hipMalloc(Clay partial plan entries)");
+        upload(&p.tiles, hp.tiles, "hipMalloc(Clay partial plan tiles)");
+    } catch (...) {  // a half-uploaded plan is never published
+        (void)hipFree(p.entries);
+        (void)hipFree(p.tiles);
+        throw;
+    }
+    return clay_partial_dev_.emplace(std::make_pair(dev, hp.depth), p).first->second;
 }
 
 const MixedDevicePlan &PatternSet::plan_for_current_device(int depth) {

@@ -3,10 +3,12 @@
 // has the formats and is HIP-free), uploaded lazily per device, and the launches that run a batch
 // whose stripes name their pattern with one byte each: in place over single-tile maps
 // (apply_mixed.hip, the RS decodes) and out of place over maps of up to kMixedMaxTiles tiles
-// (apply_map_mixed.hip, the Clay repair).
+// (apply_map_mixed.hip, the Clay repair), and the partial-sum hops of both
+// (apply_partial_mixed.hip, apply_clay_partial_mixed.hip).
 #pragma once
 
 #include "blocked_layout.hpp"
+#include "clay_partial_plan.hpp"
 #include "engine.hpp"
 #include "mixed_plan.hpp"
 #include "partial_plan.hpp"
@@ -75,11 +77,18 @@ public:
     // first-use site like plan_for_current_device.
     const PartialPlan &partial_plan(int n);
     const PartialDevicePlan &partial_plan_for_current_device(int n);
+    // The Clay partial-sum plan (clay_partial_plan.hpp: the tiled plan cut by input node) for a
+    // code of n nodes, padded for depth 4 or 8 (anything else is 4); both are built on the first
+    // call, and uploaded for the current device lazily, a first-use site like the others.
+    const ClayPartialPlan &clay_partial_plan(int n, int depth);
+    const MixedDevicePlan &clay_partial_plan_for_current_device(int n, int depth);
 
 private:
     std::vector<const CompiledMap *> maps_;
     PartialPlan partial_;  // npatterns == 0: not built yet
     std::map<int, PartialDevicePlan> partial_dev_;  // by device
+    ClayPartialPlan clay_partial4_, clay_partial8_;  // npatterns == 0: not built yet
+    std::map<std::pair<int, int>, MixedDevicePlan> clay_partial_dev_;  // (device, depth)
     MixedPlan plan4_, plan8_;
     TiledPlan tiled4_, tiled8_;
     int preferred_depth_ = 4, tiled_depth_ = 4;
@@ -115,6 +124,14 @@ void launch_apply_mixed_blocked(PatternSet &set, const uint8_t *ids, uint8_t *ba
 void launch_partial_mixed(PatternSet &set, int n, const uint8_t *ids, const uint8_t *shards, const uint8_t *in,
                           int64_t in_stripe_stride, int64_t in_shard_stride, uint8_t *acc, int64_t acc_stripe_stride,
                           int64_t acc_row_stride, int64_t nstripes, int64_t nbytes, bool is_first, hipStream_t stream);
+
+// One hop of the Clay partial-sum chain with a list and a helper node per stripe
+// (apply_clay_partial_mixed.hip k_gf_map_partial_mixed; ecx.h ecx_clay_partial_batch_mixed has the
+// meaning): `ids` and `nodes` are device byte arrays of nstripes, n the code's node count.
+void launch_clay_partial_mixed(PatternSet &set, int n, const uint8_t *ids, const uint8_t *nodes, const uint8_t *in,
+                               int64_t in_stripe_stride, int64_t in_node_stride, int64_t in_sub_stride, uint8_t *acc,
+                               int64_t acc_stripe_stride, int64_t acc_sub_stride, int64_t nstripes, int64_t nbytes,
+                               bool is_first, hipStream_t stream);
 
 // A map with a pattern per stripe, out of place (apply_map_mixed.hip k_gf_map_mixed): unit u of
 // [unit][slot][bytes] at `in` is run through records (ids[first_unit + u], 0..T) of the set's
