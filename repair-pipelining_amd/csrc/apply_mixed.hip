@@ -2,10 +2,11 @@
 // device-resident stripes that miss different shards, in one launch.
 //
 // A pattern set (mixed_plan.hpp, pattern_set.hpp) holds the decode maps of up to 256 erasure patterns
-// of one codec as one plan: the patterns' padded entry arrays back to back and 256 tile records.
+// of one codec as one plan: the patterns' padded entry arrays back to back and, every map having
+// one tile, 256 tile records.
 // One workgroup covers one (stripe, 4 KiB chunk), stripe-major.  It reads its stripe's pattern id
 // -- one byte of a device array the caller wrote -- makes it wave-uniform, and runs apply_tile
-// (apply.hpp) on record `id` exactly as k_gf_apply runs a single-tile map: the inner loop, the
+// (apply.hpp, through mixed_pass.hpp mixed_tile) on record `id` exactly as k_gf_apply runs a single-tile map: the inner loop, the
 // load ring and the split-table arithmetic are the same code.  Every byte value names a record of
 // the plan (the unused ones have no rows), so there is no bounds branch: a stripe whose record has
 // no rows -- nothing missing, or an id without a pattern -- returns before it touches the shards.
@@ -19,10 +20,7 @@
 // (launch_apply_mixed_units; mixed_launch.hpp cuts a pass into launches).
 #include <algorithm>
 
-#include "apply.hpp"
-#include "layout_probe.hpp"  // note_device_launch
-#include "mixed_launch.hpp"
-#include "pattern_set.hpp"
+#include "mixed_pass.hpp"
 
 namespace ecx {
 
@@ -34,17 +32,7 @@ __global__ void __launch_bounds__(kBlockThreads, ECX_APPLY_BOUNDS(ROWS, DEPTH)) 
     const int64_t s = (int64_t)(blockIdx.x / nc) + a.stripe_begin;
     const int64_t c = (int64_t)(blockIdx.x % nc) + a.chunk_begin;
     const uint32_t id = __builtin_amdgcn_readfirstlane((uint32_t)((const gu8 *)ids)[s]);
-    cu32 *tile = plan_ptr(a.tiles) + id * kTileDwords;
-    if (tile[2] == 0) return;  // wave-uniform: the whole workgroup leaves
-    const int64_t cbase = c * kChunkBytes;
-    int valid = 16;
-    if (SAFE) {
-        const int64_t v = a.nbytes - cbase - (int64_t)threadIdx.x * 16;
-        valid = v <= 0 ? 0 : (v >= 16 ? 16 : (int)v);
-    }
-    apply_tile<SAFE, true, SAFE ? 0 : 1, DEPTH, false, kBlockThreads, ROWS>(
-        a, tile, uniform64((uint64_t)(a.in + s * a.in_stripe_stride + cbase)),
-        uniform64((uint64_t)(a.out + s * a.out_stripe_stride + cbase)), threadIdx.x * 16, valid, nullptr);
+    mixed_tile<SAFE, DEPTH, ROWS>(a, plan_ptr(a.tiles) + id * kTileDwords, s, c, 0);
 }
 
 // The same body over one pass of a blocked batch (blocked_layout.hpp, mixed_launch.hpp): the
@@ -62,38 +50,11 @@ __global__ void __launch_bounds__(kBlockThreads, ECX_APPLY_BOUNDS(ROWS, DEPTH))
     const int64_t s = (int64_t)local_unit + a.stripe_begin;
     const int64_t c = (int64_t)(blockIdx.x % nc) + a.chunk_begin;
     const uint32_t id = __builtin_amdgcn_readfirstlane((uint32_t)((const gu8 *)ids)[verdict_quot(vd, local_unit)]);
-    cu32 *tile = plan_ptr(a.tiles) + id * kTileDwords;
-    if (tile[2] == 0) return;  // wave-uniform: the whole workgroup leaves
-    const int64_t cbase = c * kChunkBytes;
-    int valid = 16;
-    if (SAFE) {
-        const int64_t v = a.nbytes - cbase - (int64_t)threadIdx.x * 16;
-        valid = v <= 0 ? 0 : (v >= 16 ? 16 : (int)v);
-    }
-    apply_tile<SAFE, true, SAFE ? 0 : 1, DEPTH, false, kBlockThreads, ROWS>(
-        a, tile, uniform64((uint64_t)(a.in + s * a.in_stripe_stride + cbase)),
-        uniform64((uint64_t)(a.out + s * a.out_stripe_stride + cbase)), threadIdx.x * 16, valid, nullptr);
+    mixed_tile<SAFE, DEPTH, ROWS>(a, plan_ptr(a.tiles) + id * kTileDwords, s, c, 0);
 }
 
-namespace {
-// vd null: the units are the stripes, k_gf_apply_mixed reads ids[unit]
-template <bool SAFE, int D, int R>
-void launch_mixed_k(dim3 grid, hipStream_t stream, const ApplyArgs &a, const uint8_t *ids, const VerdictDiv *vd) {
-    if (vd) {
-        if (!SAFE) note_kernel("k_gf_apply_mixed_blocked", SAFE, D, R);
-        hipLaunchKernelGGL((k_gf_apply_mixed_blocked<SAFE, D, R>), grid, dim3(kBlockThreads), 0, stream, a, ids, *vd);
-        return;
-    }
-    if (!SAFE) note_kernel("k_gf_apply_mixed", SAFE, D, R);
-    hipLaunchKernelGGL((k_gf_apply_mixed<SAFE, D, R>), grid, dim3(kBlockThreads), 0, stream, a, ids);
-}
-}  // namespace
-
-// Instances: 4 or 8 accumulator rows (the set's largest pattern decides) at ring depth 4 or 8
-// for the full chunks of 16-B aligned layouts; one byte-safe instance (depth 4 -- every record of
-// either plan is padded to a multiple of 4 -- and 8 rows) for the partial last chunk and every
-// other layout.
-// There is no per-layout shape selection here: the work differs from stripe to stripe.
+// The instances are with_mixed_instance's (mixed_pass.hpp); the byte-safe one reads the same plan
+// as the full chunks (a record padded to a multiple of 8 is padded to a multiple of 4).
 //
 // The pass is `units` units of which `divisor` consecutive ones are one caller stripe, and its
 // first unit is unit `first_unit` of the whole pass `ids` describes: ids[(first_unit + u) / divisor]
@@ -105,59 +66,41 @@ void launch_apply_mixed_units(PatternSet &set, const uint8_t *ids, uint8_t *base
                               int64_t first_unit, hipStream_t stream) {
     if (units <= 0 || nbytes <= 0 || set.max_rows() == 0) return;
     if (divisor < 1 || first_unit < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "bad unit divisor");
-    // the set's own ring depth, or the one ecx_tune "depth" forces (4 / 8; others have no instance)
-    const Tuning tu = tuning();
-    const int depth = tu.depth == 4 || tu.depth == 8 ? tu.depth : set.preferred_depth();
-    const MixedPlan &hp = set.plan(depth);
-    const LaunchStreamScope scope(stream);  // first use of device state is refused under capture (engine.hpp)
-    // resident before anything is enqueued: a first use refused on a capturing stream leaves no node behind
-    const MixedDevicePlan &plan = set.plan_for_current_device(depth);
-    const uint8_t *zero_page = zero_page_for_current_device();
-    const int rows = hp.max_rows <= 4 ? 4 : kTileRows;
     // in place: the alignment conditions of a full-chunk launch are launch_rules' (BatchLayout)
     const BatchLayout b{(uintptr_t)base, (uintptr_t)base, stripe_stride, slot_stride, stripe_stride,
                         slot_stride,     units,           nbytes,        false};
-    const int64_t full = b.aligned16() ? nbytes / kChunkBytes : 0;
-    const int64_t rest = (nbytes - full * kChunkBytes + kChunkBytes - 1) / kChunkBytes;
-    if (full + rest > kMixedMaxBlocks) throw Error(ECX_E_ILLEGAL_ARGUMENT, "byte_count is too large for one launch");
-
-    ApplyArgs a{};
-    a.in = base;
-    a.out = base;
-    a.entries = plan.entries;
-    a.tiles = plan.tiles;
-    a.zero_page = zero_page;
-    a.in_stripe_stride = a.out_stripe_stride = stripe_stride;
-    a.in_slot_stride = a.out_slot_stride = slot_stride;
-    a.nbytes = nbytes;
-    a.n_tiles = 1;
-    a.tail_chunk = -1;
-    auto run = [&](bool safe, int64_t chunk_begin, int64_t n_chunks) {
-        if (n_chunks <= 0) return;
-        a.chunk_begin = chunk_begin;
-        a.n_chunks = n_chunks;
-        for_mixed_launches(units, n_chunks, divisor, first_unit, kMixedMaxBlocks, [&](const MixedLaunch &l) {
-            a.stripe_begin = l.unit_begin;
-            const dim3 grid((unsigned)(l.unit_count * n_chunks));
-            // divisor 1: k_gf_apply_mixed indexes its ids by unit_begin + the local unit itself
-            const uint8_t *lids = divisor > 1 ? ids + l.id_begin : ids + first_unit;
-            const VerdictDiv *vd = divisor > 1 ? &l.vd : nullptr;
-            if (safe) launch_mixed_k<true, 4, kTileRows>(grid, stream, a, lids, vd);
-            else if (rows == 4 && depth == 8) launch_mixed_k<false, 8, 4>(grid, stream, a, lids, vd);
-            else if (rows == 4) launch_mixed_k<false, 4, 4>(grid, stream, a, lids, vd);
-            else if (depth == 8) launch_mixed_k<false, 8, kTileRows>(grid, stream, a, lids, vd);
-            else launch_mixed_k<false, 4, kTileRows>(grid, stream, a, lids, vd);
-        });
-    };
-    run(false, 0, full);
-    run(true, full, rest);
-    check_hip(hipGetLastError(), "k_gf_apply_mixed launch");
-    int dev = 0;
-    check_hip(hipGetDevice(&dev), "hipGetDevice");
+    MixedPass pass{units, nbytes, divisor, first_unit, 1, b.aligned16(), set.max_rows(), set.preferred_depth()};
+    pass.too_large = "byte_count is too large for one launch";
+    pass.what = "k_gf_apply_mixed launch";
     // (input bytes, for the launch registry: as if every stripe read its longest pattern)
+    const TiledPlan &hp = set.plan(4);
     uint32_t inputs = 0;
     for (int p = 0; p < hp.npatterns; ++p) inputs = std::max(inputs, hp.tiles[(size_t)p * kTileDwords + 3]);
-    note_device_launch(dev, stream, units * nbytes * (int64_t)inputs);
+    pass.inputs = inputs;
+
+    ApplyArgs a = mixed_apply_args(base, stripe_stride, slot_stride, base, stripe_stride, slot_stride, nbytes, 1, false);
+    const PatternDevicePlan *plan = nullptr;
+    run_mixed_pass(
+        pass, stream,
+        [&](int depth, int64_t, int64_t) {
+            plan = &set.plan_for_current_device(depth, "the pattern set's device plan");
+            a.tiles = plan->records;
+            a.zero_page = zero_page_for_current_device();
+        },
+        [&](auto safe, auto depth, auto rows, const MixedStep &st) {
+            constexpr bool SAFE = decltype(safe)::value;
+            constexpr int D = decltype(depth)::value, R = decltype(rows)::value;
+            st.aim(a, *plan);
+            if (divisor > 1) {
+                if (!SAFE) note_kernel("k_gf_apply_mixed_blocked", SAFE, D, R);
+                hipLaunchKernelGGL((k_gf_apply_mixed_blocked<SAFE, D, R>), st.grid, dim3(kBlockThreads), 0, stream, a,
+                                   ids + st.l.id_begin, st.l.vd);
+                return;
+            }
+            // divisor 1: k_gf_apply_mixed indexes its ids by unit_begin + the local unit itself
+            if (!SAFE) note_kernel("k_gf_apply_mixed", SAFE, D, R);
+            hipLaunchKernelGGL((k_gf_apply_mixed<SAFE, D, R>), st.grid, dim3(kBlockThreads), 0, stream, a, ids + first_unit);
+        });
 }
 
 void launch_apply_mixed(PatternSet &set, const uint8_t *ids, uint8_t *base, int64_t stripe_stride,

@@ -14,12 +14,7 @@
 // accumulator row a store, XORed with the old row when the hop accumulates.  The old rows are
 // loaded right behind the input, ahead of the multiply, so all of a lane's loads are in flight
 // together; the stripe's row count and the hop's mode select a straight-line body for that.
-#include <algorithm>
-
-#include "apply.hpp"
-#include "layout_probe.hpp"  // note_device_launch
-#include "mixed_launch.hpp"
-#include "pattern_set.hpp"
+#include "mixed_pass.hpp"
 
 namespace ecx {
 
@@ -100,37 +95,23 @@ __global__ void __launch_bounds__(kBlockThreads, ROWS <= 4 ? 8 : 4) k_gf_partial
     else partial_rows_of<SAFE, ROWS, false>(nrows, ent, ip, ap, a.acc_row_stride, valid);
 }
 
-namespace {
-template <bool SAFE, int R>
-void launch_partial_k(dim3 grid, hipStream_t stream, const PartialArgs &a) {
-    if (!SAFE) note_kernel("k_gf_partial_mixed", SAFE, R);
-    hipLaunchKernelGGL((k_gf_partial_mixed<SAFE, R>), grid, dim3(kBlockThreads), 0, stream, a);
-}
-}  // namespace
-
-// Instances: 4 or 8 accumulator rows (the set's largest pattern decides) for the full chunks of
-// 16-B aligned layouts; one byte-safe instance (8 rows) for the partial last chunk and every other
-// layout.  mixed_launch.hpp cuts the batch into launches (divisor 1: the units are the stripes).
+// Instances: with_mixed_instance's rows (mixed_pass.hpp) -- 4 or 8 for the full chunks of 16-B
+// aligned layouts, one byte-safe instance of 8 -- and no ring depth.  mixed_launch.hpp cuts the
+// batch into launches (divisor 1: the units are the stripes).
 void launch_partial_mixed(PatternSet &set, int n, const uint8_t *ids, const uint8_t *shards, const uint8_t *in,
                           int64_t in_stripe_stride, int64_t in_shard_stride, uint8_t *acc, int64_t acc_stripe_stride,
                           int64_t acc_row_stride, int64_t nstripes, int64_t nbytes, bool is_first, hipStream_t stream) {
     if (nstripes <= 0 || nbytes <= 0 || set.max_rows() == 0) return;
     const PartialPlan &hp = set.partial_plan(n);
-    const LaunchStreamScope scope(stream);  // first use of device state is refused under capture (engine.hpp)
-    // resident before anything is enqueued: a first use refused on a capturing stream leaves no node behind
-    const PartialDevicePlan &plan = set.partial_plan_for_current_device(n);
-    const int rows = hp.max_rows <= 4 ? 4 : kTileRows;
     const BatchLayout b{(uintptr_t)in,     (uintptr_t)acc, in_stripe_stride, in_shard_stride, acc_stripe_stride,
                         acc_row_stride,    nstripes,       nbytes,           !is_first};
-    const int64_t full = b.aligned16() ? nbytes / kChunkBytes : 0;
-    const int64_t rest = (nbytes - full * kChunkBytes + kChunkBytes - 1) / kChunkBytes;
-    if (full + rest > kMixedMaxBlocks) throw Error(ECX_E_ILLEGAL_ARGUMENT, "byte_count is too large for one launch");
+    MixedPass pass{nstripes, nbytes, 1, 0, 1, b.aligned16(), hp.max_rows};
+    pass.too_large = "byte_count is too large for one launch";
+    pass.what = "k_gf_partial_mixed launch";
 
     PartialArgs a{};
     a.in = in;
     a.acc = acc;
-    a.entries = plan.entries;
-    a.rows = plan.rows;
     a.ids = ids;
     a.shards = shards;
     a.in_stripe_stride = in_stripe_stride;
@@ -140,24 +121,20 @@ void launch_partial_mixed(PatternSet &set, int n, const uint8_t *ids, const uint
     a.nbytes = nbytes;
     a.n = (uint32_t)n;
     a.accumulate = is_first ? 0 : 1;
-    auto run = [&](bool safe, int64_t chunk_begin, int64_t n_chunks) {
-        if (n_chunks <= 0) return;
-        a.chunk_begin = chunk_begin;
-        a.n_chunks = n_chunks;
-        for_mixed_launches(nstripes, n_chunks, 1, 0, kMixedMaxBlocks, [&](const MixedLaunch &l) {
-            a.stripe_begin = l.unit_begin;
-            const dim3 grid((unsigned)(l.unit_count * n_chunks));
-            if (safe) launch_partial_k<true, kTileRows>(grid, stream, a);
-            else if (rows == 4) launch_partial_k<false, 4>(grid, stream, a);
-            else launch_partial_k<false, kTileRows>(grid, stream, a);
+    const PatternDevicePlan *plan = nullptr;
+    run_mixed_pass(
+        pass, stream,
+        [&](int, int64_t, int64_t) {
+            plan = &set.partial_plan_for_current_device(n);
+            a.rows = plan->records;
+        },
+        [&](auto safe, auto, auto rows, const MixedStep &st) {
+            constexpr bool SAFE = decltype(safe)::value;
+            constexpr int R = decltype(rows)::value;
+            st.aim(a, *plan);
+            if (!SAFE) note_kernel("k_gf_partial_mixed", SAFE, R);
+            hipLaunchKernelGGL((k_gf_partial_mixed<SAFE, R>), st.grid, dim3(kBlockThreads), 0, stream, a);
         });
-    };
-    run(false, 0, full);
-    run(true, full, rest);
-    check_hip(hipGetLastError(), "k_gf_partial_mixed launch");
-    int dev = 0;
-    check_hip(hipGetDevice(&dev), "hipGetDevice");
-    note_device_launch(dev, stream, nstripes * nbytes);  // (input bytes, for the launch registry)
 }
 
 }  // namespace ecx

@@ -6,47 +6,6 @@
 
 namespace ecx {
 
-int mixed_depth(const MixedPatternIn *patterns, int npatterns) {
-    uint32_t min_count = 0xFFFFFFFFu;
-    for (int p = 0; p < npatterns; ++p) {
-        const uint32_t c = patterns[p].tile[1];
-        if (c > 0) min_count = std::min(min_count, c);
-    }
-    return min_count != 0xFFFFFFFFu && min_count >= 12 ? 8 : 4;
-}
-
-bool build_mixed_plan(const MixedPatternIn *patterns, int npatterns, int depth, MixedPlan *out) {
-    if (!patterns || !out || npatterns < 1 || npatterns > kMixedRecords || depth <= 0) return false;
-    for (int p = 0; p < npatterns; ++p) {
-        if (!patterns[p].tile || !patterns[p].entries) return false;
-        if (patterns[p].tile[2] > (uint32_t)kMixedTileRows) return false;
-    }
-    MixedPlan m;
-    m.npatterns = npatterns;
-    m.depth = depth;
-    m.tiles.assign((size_t)kMixedRecords * kMixedTileDwords, 0u);
-    for (int p = 0; p < npatterns; ++p) {
-        const uint32_t *src = patterns[p].tile;
-        uint32_t *tile = m.tiles.data() + (size_t)p * kMixedTileDwords;
-        const uint32_t begin = src[0], count = src[1];
-        std::copy(src, src + kMixedTileDwords, tile);
-        tile[0] = (uint32_t)(m.entries.size() / kMixedEntryDwords);
-        m.entries.insert(m.entries.end(), patterns[p].entries + (size_t)begin * kMixedEntryDwords,
-                         patterns[p].entries + (size_t)(begin + count) * kMixedEntryDwords);
-        const uint32_t padded = (count + (uint32_t)depth - 1) / (uint32_t)depth * (uint32_t)depth;
-        for (uint32_t d = count; d < padded; ++d) {
-            uint32_t rec[kMixedEntryDwords] = {0};
-            rec[0] = kMixedDummySlot;
-            m.entries.insert(m.entries.end(), rec, rec + kMixedEntryDwords);
-        }
-        tile[1] = padded;
-        m.max_rows = std::max(m.max_rows, (int)src[2]);
-    }
-    if (m.entries.empty()) m.entries.assign(kMixedEntryDwords, 0u);
-    *out = std::move(m);
-    return true;
-}
-
 namespace {
 
 // One record of a plan applied to one stripe, as apply_tile reads it: `in` is only read, the
@@ -86,11 +45,6 @@ bool emulate_record(const std::vector<uint32_t> &entries, const uint32_t *tile, 
 }
 
 }  // namespace
-
-bool emulate_mixed(const MixedPlan &p, uint8_t id, const uint8_t *in, uint8_t *out, int64_t len) {
-    if (p.tiles.size() != (size_t)kMixedRecords * kMixedTileDwords || p.depth <= 0) return false;
-    return emulate_record(p.entries, p.tiles.data() + (size_t)id * kMixedTileDwords, p.depth, in, out, len);
-}
 
 int tiled_depth(const TiledPatternIn *patterns, int npatterns) {
     uint32_t min_count = 0xFFFFFFFFu;

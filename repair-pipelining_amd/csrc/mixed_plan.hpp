@@ -1,20 +1,25 @@
 // mixed_plan.hpp -- the device plan of a pattern set (include/ecx.h ecx_rs_pattern_set,
-// DESIGN.md section 4.7): several single-tile maps of one codec, one per erasure pattern,
-// concatenated so that one launch decodes stripes that miss different shards.
+// ecx_clay_pattern_set; DESIGN.md sections 4.7 and 4.7.3): several maps of one codec, one per
+// erasure pattern, concatenated so that one launch runs stripes that each name their own.
 //
 // The plan is the one k_gf_apply reads (engine.hpp: entries of kEntryDwords, tile records of
 // kTileDwords), with two differences:
-//   * the entry arrays of the patterns lie back to back, each padded to a multiple of the set's
-//     load-ring depth with zero-coefficient kDummySlot entries, and record p's first-entry
-//     index is rebased into that array;
-//   * there are always kMixedRecords (256) tile records.  Record p < npatterns is pattern p's;
-//     the rest are empty (0 entries, 0 rows).  A stripe names its pattern with one byte, so
-//     every value that byte can hold selects a record inside the plan: k_gf_apply_mixed
-//     (apply_mixed.hip) needs no bounds branch, and an id without a pattern does nothing.
+//   * the entry arrays of the patterns' tiles lie back to back in (pattern, tile) order, each
+//     padded to a multiple of the set's load-ring depth with zero-coefficient kDummySlot entries,
+//     and every record's first-entry index is rebased into that array;
+//   * the record array is [kMixedRecords][T], T the largest tile count among the set's maps
+//     (1..kMixedMaxTiles): record (id, t) at (id * T + t) * kMixedTileDwords is tile t of pattern
+//     id.  Every record past a pattern's own tile count and every record of an id >= npatterns is
+//     empty (0 entries, 0 rows).  A stripe names its pattern with one byte, so every
+//     (id byte, tile < T) pair selects a record inside the plan: the kernels need no bounds
+//     branch, and an id without a pattern does nothing.
+// A set of single-tile maps (the RS decodes) has T == 1 and 256 records: k_gf_apply_mixed
+// (apply_mixed.hip) reads record `id`, in place.  A set with a map of several tiles (Clay repair
+// of two nodes: 16 rows) runs out of place only (apply_map_mixed.hip k_gf_map_mixed).
 //
 // No HIP header and no other unit of the engine: the plan and its interpreter run -- and are
-// tested -- on the CPU (tests/native/mixed_plan_check.cpp).  The constants repeat engine.hpp's;
-// engine.cpp asserts that they agree.
+// tested -- on the CPU (tests/native/mixed_plan_check.cpp, tiled_plan_check.cpp).  The constants
+// repeat engine.hpp's; pattern_set.hpp asserts that they agree.
 #pragma once
 
 #include <cstdint>
@@ -27,47 +32,6 @@ constexpr int kMixedEntryDwords = 48;
 constexpr int kMixedTileDwords = 16;
 constexpr int kMixedTileRows = 8;
 constexpr uint32_t kMixedDummySlot = 0xFFFFFFFFu;
-
-// One pattern's single-tile map as CompiledMap holds it: `tile` is its tile record (kTileDwords:
-// [0] first entry [1] entry count [2] rows [4..4+rows) output slots) and `entries` the entry
-// array that record indexes, unpadded.  A map with no rows has a record of zeros.
-struct MixedPatternIn {
-    const uint32_t *entries = nullptr;
-    const uint32_t *tile = nullptr;
-};
-
-struct MixedPlan {
-    std::vector<uint32_t> entries;  // padded, concatenated; never empty (one zero entry at least)
-    std::vector<uint32_t> tiles;    // kMixedRecords * kMixedTileDwords
-    int npatterns = 0;
-    int depth = 4;     // every record's entry count is a multiple of it
-    int max_rows = 0;  // the largest row count of the set: which ROWS instance can run it
-};
-
-// The load-ring depth of a set, by CompiledMap::preferred_depth's rule: 8 only if every
-// non-empty pattern has at least 12 entries, else 4.
-int mixed_depth(const MixedPatternIn *patterns, int npatterns);
-
-// Builds the plan for `depth`.  False -- and *out untouched -- when npatterns is outside
-// 1..kMixedRecords, depth is not positive, a pointer is null or a record has more than
-// kMixedTileRows rows.
-bool build_mixed_plan(const MixedPatternIn *patterns, int npatterns, int depth, MixedPlan *out);
-
-// The plan applied to one stripe as k_gf_apply_mixed reads it for pattern id `id` (any byte):
-// `in` and `out` are [slot][len]; padding entries read zeros; only the record's output slots are
-// written.  False when the record breaks the plan's invariants (entry count not a multiple of
-// the depth, a padding entry with coefficients, entries outside the array).
-bool emulate_mixed(const MixedPlan &p, uint8_t id, const uint8_t *in, uint8_t *out, int64_t len);
-
-// ---- the tiled form (apply_map_mixed.hip k_gf_map_mixed) ----
-//
-// A set whose maps have several tiles (Clay repair of two nodes: 16 rows).  T, the tiles per
-// pattern, is the largest tile count among the set's maps, 1..kMixedMaxTiles.  The record array is
-// [kMixedRecords][T]: record (id, t) at (id * T + t) * kMixedTileDwords is tile t of pattern id;
-// every record past a pattern's own tile count and every record of an id >= npatterns is empty, so
-// every (id byte, tile < T) pair selects a record inside the plan.  The entries are those of the
-// mixed plan: each tile's padded to the depth, back to back in (pattern, tile) order, first-entry
-// indices rebased.  With T == 1 the arrays are build_mixed_plan's bit for bit.
 constexpr int kMixedMaxTiles = 8;
 
 // One pattern's map as CompiledMap holds it: `tiles` are its n_tiles tile records (kTileDwords
@@ -89,17 +53,21 @@ struct TiledPlan {
     int max_out_slot = -1;  // the largest output slot of any tile
 };
 
-// mixed_depth's rule over every non-empty tile of the set.
+// The load-ring depth of a set, by CompiledMap::preferred_depth's rule: 8 only if every
+// non-empty tile of the set has at least 12 entries, else 4.
 int tiled_depth(const TiledPatternIn *patterns, int npatterns);
 
-// Builds the tiled plan for `depth`.  False -- and *out untouched -- when npatterns is outside
+// Builds the plan for `depth`.  False -- and *out untouched -- when npatterns is outside
 // 1..kMixedRecords, depth is not positive, a pointer is null, a pattern has more than
 // kMixedMaxTiles tiles or a tile more than kMixedTileRows rows.
 bool build_tiled_plan(const TiledPatternIn *patterns, int npatterns, int depth, TiledPlan *out);
 
-// The tiled plan applied to one stripe as k_gf_map_mixed reads it for pattern id `id` (any byte),
-// out of place: `in` is [slot][len] and is only read, `out` is [slot][len] and only the output
-// slots of the id's records are written.  False when a record breaks the plan's invariants.
+// The plan applied to one stripe as k_gf_map_mixed reads it for pattern id `id` (any byte), out of
+// place: `in` is [slot][len] and is only read, `out` is [slot][len] and only the output slots of
+// the id's records are written; padding entries read zeros.  With T == 1, `in` and `out` may be
+// two copies of one stripe: that is k_gf_apply_mixed.  False when a record breaks the plan's
+// invariants (entry count not a multiple of the depth, a padding entry with coefficients, entries
+// outside the array).
 bool emulate_tiled(const TiledPlan &p, uint8_t id, const uint8_t *in, uint8_t *out, int64_t len);
 
 }  // namespace ecx

@@ -1,6 +1,7 @@
-// mixed_plan_check.cpp -- the device plan of a pattern set (csrc/mixed_plan.cpp), on the CPU:
-// built from that file and csrc/gf.cpp (the field's tables) with no ROCm include path
-// (tests/test_mixed_plan_native.py).
+// mixed_plan_check.cpp -- the device plan of a pattern set (csrc/mixed_plan.cpp) with one tile per
+// pattern, the form the in-place RS kernels read, on the CPU: built from that file and csrc/gf.cpp
+// (the field's tables) with no ROCm include path (tests/test_mixed_plan_native.py;
+// tests/native/tiled_plan_check.cpp has the plans of several tiles).
 //
 // Synthetic single-tile maps of 1, 3, 4, 12 and 17 entries (and one with no rows) are compiled
 // into sets at load-ring depths 4 and 8.  Asserted: every record's rebased first index and padded
@@ -60,7 +61,8 @@ struct Pattern {
     std::vector<uint8_t> coef;  // [rows][count]
     std::vector<uint32_t> entries;
     uint32_t tile[kMixedTileDwords] = {0};
-    MixedPatternIn in() const { return MixedPatternIn{entries.data(), tile}; }
+    // (a map without rows still has one record, of zeros)
+    TiledPatternIn in() const { return TiledPatternIn{entries.data(), tile, 1}; }
 };
 
 static Pattern make_pattern(int count, int rows, int lead, std::mt19937_64 &rng) {
@@ -113,11 +115,11 @@ static void direct(const Pattern &p, const uint8_t *in, uint8_t *out, int64_t le
 }
 
 static void check_set(const std::vector<Pattern> &pats, int depth, std::mt19937_64 &rng) {
-    std::vector<MixedPatternIn> ins;
+    std::vector<TiledPatternIn> ins;
     for (const Pattern &p : pats) ins.push_back(p.in());
-    MixedPlan plan;
-    REQUIRE(build_mixed_plan(ins.data(), (int)ins.size(), depth, &plan));
-    REQUIRE(plan.npatterns == (int)pats.size() && plan.depth == depth);
+    TiledPlan plan;
+    REQUIRE(build_tiled_plan(ins.data(), (int)ins.size(), depth, &plan));
+    REQUIRE(plan.npatterns == (int)pats.size() && plan.depth == depth && plan.tiles_per_pattern == 1);
     REQUIRE(plan.tiles.size() == (size_t)kMixedRecords * kMixedTileDwords);
     REQUIRE(plan.entries.size() % kMixedEntryDwords == 0 && !plan.entries.empty());
 
@@ -162,16 +164,16 @@ static void check_set(const std::vector<Pattern> &pats, int depth, std::mt19937_
     for (int id = 0; id < kMixedRecords; ++id) {
         if (id >= (int)pats.size() && id != (int)pats.size() && id != 255) continue;  // the first empty id and 255
         std::vector<uint8_t> got = stripe;
-        REQUIRE(emulate_mixed(plan, (uint8_t)id, stripe.data(), got.data(), len));
+        REQUIRE(emulate_tiled(plan, (uint8_t)id, stripe.data(), got.data(), len));
         std::vector<uint8_t> want = stripe;
         if (id < (int)pats.size()) {
             direct(pats[id], stripe.data(), want.data(), len);
             // the pattern's own padded plan: a set of that one pattern, record 0
-            MixedPlan own;
-            const MixedPatternIn one = pats[id].in();
-            REQUIRE(build_mixed_plan(&one, 1, depth, &own));
+            TiledPlan own;
+            const TiledPatternIn one = pats[id].in();
+            REQUIRE(build_tiled_plan(&one, 1, depth, &own));
             std::vector<uint8_t> alone = stripe;
-            REQUIRE(emulate_mixed(own, 0, stripe.data(), alone.data(), len));
+            REQUIRE(emulate_tiled(own, 0, stripe.data(), alone.data(), len));
             REQUIRE(alone == got);
         }
         REQUIRE(got == want);  // inputs and every other slot untouched, outputs as computed
@@ -207,9 +209,9 @@ int main() {
         const Pattern p1 = make_pattern(1, 1, 0, rng), p12 = make_pattern(12, 4, 0, rng), p17 = make_pattern(17, 3, 2, rng),
                       p11 = make_pattern(11, 2, 0, rng), p0 = make_pattern(0, 0, 0, rng);
         auto depth_of = [](std::vector<const Pattern *> v) {
-            std::vector<MixedPatternIn> ins;
+            std::vector<TiledPatternIn> ins;
             for (const Pattern *p : v) ins.push_back(p->in());
-            return mixed_depth(ins.data(), (int)ins.size());
+            return tiled_depth(ins.data(), (int)ins.size());
         };
         REQUIRE(depth_of({&p12, &p17}) == 8);
         REQUIRE(depth_of({&p12, &p0, &p17}) == 8);
@@ -221,24 +223,26 @@ int main() {
     // refusals leave *out untouched
     {
         const Pattern p = make_pattern(3, 2, 0, rng);
-        const MixedPatternIn one = p.in();
-        MixedPlan plan;
+        const TiledPatternIn one = p.in();
+        TiledPlan plan;
         plan.npatterns = -7;
-        REQUIRE(!build_mixed_plan(&one, 0, 4, &plan));
-        REQUIRE(!build_mixed_plan(&one, kMixedRecords + 1, 4, &plan));
-        REQUIRE(!build_mixed_plan(&one, 1, 0, &plan));
-        REQUIRE(!build_mixed_plan(nullptr, 1, 4, &plan));
+        REQUIRE(!build_tiled_plan(&one, 0, 4, &plan));
+        REQUIRE(!build_tiled_plan(&one, kMixedRecords + 1, 4, &plan));
+        REQUIRE(!build_tiled_plan(&one, 1, 0, &plan));
+        REQUIRE(!build_tiled_plan(nullptr, 1, 4, &plan));
+        const TiledPatternIn no_tiles{p.entries.data(), nullptr, 1};
+        REQUIRE(!build_tiled_plan(&no_tiles, 1, 4, &plan));
         Pattern wide = p;
         wide.tile[2] = kMixedTileRows + 1;
-        const MixedPatternIn w = wide.in();
-        REQUIRE(!build_mixed_plan(&w, 1, 4, &plan));
+        const TiledPatternIn w = wide.in();
+        REQUIRE(!build_tiled_plan(&w, 1, 4, &plan));
         REQUIRE(plan.npatterns == -7 && plan.tiles.empty());
         // the interpreter refuses a record that is not padded to the plan's depth
-        REQUIRE(build_mixed_plan(&one, 1, 4, &plan));
+        REQUIRE(build_tiled_plan(&one, 1, 4, &plan));
         plan.depth = 8;
         std::vector<uint8_t> s((size_t)kSlots * 4, 1), o = s;
-        REQUIRE(!emulate_mixed(plan, 0, s.data(), o.data(), 4));
-        REQUIRE(emulate_mixed(plan, 9, s.data(), o.data(), 4) && o == s);
+        REQUIRE(!emulate_tiled(plan, 0, s.data(), o.data(), 4));
+        REQUIRE(emulate_tiled(plan, 9, s.data(), o.data(), 4) && o == s);
     }
     std::printf("mixed_plan_check: ok (%ld checks)\n", g_checks);
     return 0;
