@@ -231,6 +231,41 @@ int ecx_rs_decode_missing_blocked_batch(ecx_rs *rs, const uint8_t *shard_present
 int ecx_rs_is_parity_correct_blocked_batch(ecx_rs *rs, const uint8_t *base, int64_t nstripes, int64_t byte_count,
                                            int64_t block_bytes, uint8_t *verdict, void *stream);
 
+/* Which shard is corrupt in a stripe that fails ReedSolomon.isParityCorrect
+ * (ReedSolomon.java:129-178)?  The reference has no counterpart; this is the engine's, the step
+ * between the scrub and the repair.  Layout of ecx_rs_is_parity_correct_batch, read-only, over bytes
+ * [offset, offset + byte_count) of stripe s:
+ *   suspect[s][j] (a device byte array [nstripes][n]) = 1 when replacing shard j alone can make the
+ *                 stripe pass isParityCorrect, else 0;
+ *   culprit[s]    (a device int32 array of nstripes) = -1: the stripe is clean, all n suspects are 1;
+ *                 j: exactly one suspect; -2: no single shard explains the stripe, no suspect is 1;
+ *   heal_id[s]    (a device byte array of nstripes, or NULL: not wanted) = j when culprit[s] == j,
+ *                 else 255.
+ * Pattern j of the set made from the n patterns "shard j missing" (1 - identity) rebuilds shard j,
+ * and id 255 has no pattern there, so ecx_rs_decode_missing_batch_mixed(that set, heal_id, ...) on
+ * the same stream heals the batch with no host round trip.  With H = [P | I] the m x n check matrix
+ * and S(b) = H x(b) the syndromes at byte b, shard j explains the stripe exactly when S(b) is a
+ * multiple of column H_j at every b; the kernel tests that on the syndromes the check already holds
+ * in registers, so a clean stripe costs what the check costs.
+ * What the answer means: with m = 2 two corrupt shards at the SAME byte position can imitate a
+ * third shard (a CPU probe against the oracle's brute force saw it in 2 of 45 cases for RS(4,2) and
+ * 6 of 30 for RS(3,2)), and healing then rewrites a good shard from bad ones.  For m >= 3 the probe
+ * saw no such case: a code of distance m + 1 tells two errors from one.
+ * ECX_E_ILLEGAL_ARGUMENT: m < 2 (every column matches every syndrome), m > 8 (the check map is no
+ * longer one tile), heal_id wanted with n > 255, a negative count.  The pointers are checked after
+ * the counts (ECX_E_NULL).  nstripes == 0 touches nothing; byte_count == 0 makes every stripe clean.
+ * The first call of a codec on a device uploads its plans and must be made outside stream capture. */
+int ecx_rs_locate_corrupt_batch(ecx_rs *rs, const uint8_t *base, int64_t stripe_stride, int64_t shard_stride,
+                                int64_t nstripes, int64_t offset, int64_t byte_count, uint8_t *suspect,
+                                int32_t *culprit, uint8_t *heal_id, void *stream);
+/* The same over the blocked layout (ecx_rs_is_parity_correct_blocked_batch's arguments; isParityCorrect,
+ * ReedSolomon.java:129-178, on the stripe's natural shards over [0, byte_count)): the layout's two
+ * passes clear the suspects of unit / full's stripe, so a shard stays a suspect when it explains
+ * every block of its stripe and the tail.  heal_id feeds ecx_rs_decode_missing_blocked_batch_mixed. */
+int ecx_rs_locate_corrupt_blocked_batch(ecx_rs *rs, const uint8_t *base, int64_t nstripes, int64_t byte_count,
+                                        int64_t block_bytes, uint8_t *suspect, int32_t *culprit, uint8_t *heal_id,
+                                        void *stream);
+
 /* The same two blocked batches (encodeParity / decodeMissing, ReedSolomon.java:94-108, :189-286)
  * from HOST memory, in place (base: nstripes * n * byte_count bytes of
  * pageable or pinned host memory in the blocked layout): the full blocks, then the tails, each a

@@ -151,6 +151,10 @@ RULES = {
     "ecx_rs_index_patterns": ((), [NN("shards", "nstripes", "cap"), A("present", "(int64_t)nstripes * shards"),
                                    A("patterns", "(int64_t)cap * shards"), A("npatterns", "1"),
                                    A("ids", "nstripes")]),
+    # the locate takes device addresses only (heal_id 0 = not wanted); its counts are refused here as
+    # the exports do
+    "ecx_rs_locate_corrupt_batch": ((), [NN("nstripes", "offset", "byte_count")]),
+    "ecx_rs_locate_corrupt_blocked_batch": ((), [NN("nstripes", "byte_count")]),
     "ecx_rs_blocked_layout": ((), [A("layout", "3")]),
     "ecx_rs_recommended_pitch": ((), [A("pitch", "1")]),
     "ecx_rs_decode_missing_blocked_batch": (("rs",), [A("shard_present", RS_N)]),
@@ -386,6 +390,8 @@ def classify(fn, ctype, pname):
         if is_address_fn(fn) and not pname.endswith("_present"):
             return "addr", "long", "jlong"
         return "bytes", "byte[]", "jbyteArray"
+    if base == "int32_t*" and is_address_fn(fn):  # a device int32 array (the locate's culprits)
+        return "addr", "long", "jlong"
     if base == "int*":
         return "ints", "int[]", "jintArray"
     if base == "int64_t*":

@@ -814,6 +814,48 @@ class ReedSolomon:
                                                                         byteCount, blockBytes, _host_ptr(verdict),
                                                                         arr.ctypes.data, len(devs)))
 
+    def _check_locate_outputs(self, nstripes, suspect, culprit, healId):
+        n = self.getTotalShardCount()
+        _check_layout(suspect, n, 0, 0, nstripes, n, "suspect")
+        _check_layout(culprit, 4, 0, 0, nstripes, 4, "culprit")
+        if healId is not None:
+            _check_layout(healId, 1, 0, 0, nstripes, 1, "healId")
+
+    def locateCorruptBatch(self, shards, stripe_stride, shard_stride, nstripes, firstByte, byteCount, suspect,
+                           culprit, healId=None, stream=None) -> None:
+        """Which shard of each stripe that fails isParityCorrect is corrupt, read-only
+        (ecx_rs_locate_corrupt_batch; layout of isParityCorrectBatch, bytes [firstByte, firstByte +
+        byteCount)).  ``suspect`` (device uint8 [nstripes][n]) receives 1 where replacing that shard
+        alone can make the stripe pass; ``culprit`` (device int32, nstripes) -1 for a clean stripe,
+        j for exactly one suspect, -2 when no single shard explains the stripe; ``healId`` (device
+        uint8, nstripes, or None) j or 255 -- the ids that decodeMissingBatchMixed takes with
+        singleLossPatternSet() to heal the batch on the same stream.  Codes with 2 <= m <= 8."""
+        _check_layout(shards, stripe_stride, shard_stride, self.getTotalShardCount() - 1, nstripes,
+                      firstByte + byteCount, "shards")
+        self._check_locate_outputs(nstripes, suspect, culprit, healId)
+        check(lib().ecx_rs_locate_corrupt_batch(self._h, _dev_ptr(shards), stripe_stride, shard_stride, nstripes,
+                                                firstByte, byteCount, _dev_ptr(suspect), _dev_ptr(culprit),
+                                                None if healId is None else _dev_ptr(healId), _stream(stream)))
+
+    def locateCorruptBlockedBatch(self, base, nstripes, byteCount, suspect, culprit, healId=None, blockBytes=0,
+                                  stream=None) -> None:
+        """locateCorruptBatch over nstripes device-resident stripes in the blocked layout
+        (ecx_rs_locate_corrupt_blocked_batch; blockBytes 0 = the recommended block), over bytes
+        [0, byteCount) of the natural shards; ``healId`` feeds decodeMissingBlockedBatchMixed."""
+        _check_extent(base, nstripes * self.getTotalShardCount() * byteCount, "base")
+        self._check_locate_outputs(nstripes, suspect, culprit, healId)
+        check(lib().ecx_rs_locate_corrupt_blocked_batch(self._h, _dev_ptr(base), nstripes, byteCount, blockBytes,
+                                                        _dev_ptr(suspect), _dev_ptr(culprit),
+                                                        None if healId is None else _dev_ptr(healId),
+                                                        _stream(stream)))
+
+    def singleLossPatternSet(self) -> "PatternSet":
+        """The n patterns "shard j missing", in shard order (1 - eye(n)): pattern j rebuilds shard
+        j, so locateCorruptBatch's healId names the pattern that heals each stripe, and 255 -- no
+        pattern of this set -- leaves a stripe untouched."""
+        n = self.getTotalShardCount()
+        return self.patternSet(1 - np.eye(n, dtype=np.uint8))
+
     def decodeMissingBatch(self, shards, shardPresent, stripe_stride, shard_stride, nstripes, offset, byteCount,
                            stream=None):
         """decodeMissing over nstripes device-resident stripes, in place (ecx_rs_decode_missing_batch)."""

@@ -1,5 +1,6 @@
 // apply_check_body.inc -- the body of k_gf_check and k_gf_check_blocked (apply_check.hip), over
-// the kernel's ApplyArgs `a`.  ECX_CHECK_VERDICT(s) is the verdict index of stripe (unit) s.
+// the kernel's ApplyArgs `a`, and stage one of k_gf_locate and k_gf_locate_blocked (apply_locate.hip).
+// ECX_CHECK_VERDICT(s) is the verdict index of stripe (unit) s.
 // Included text, not a shared __device__ function: routed through one, the natural layout's
 // instantiations came out with other register counts than before (two more VGPRs and one wave
 // less per SIMD on <true, 4, 8>); as text they are instruction for instruction what they were.
@@ -53,8 +54,10 @@
 #pragma unroll
     for (int o = 0; o < ROWS; ++o)
         if (o < nrows) nz |= acc[o].x | acc[o].y | acc[o].z | acc[o].w;
+#ifndef ECX_CHECK_KEEP_SYNDROMES  // (k_gf_locate, apply_locate.hip, goes on from acc[] and nz itself)
     // one vector byte store per wave that saw a mismatch (every writer stores the same 0)
     if (__builtin_amdgcn_ballot_w64(nz != 0) && (threadIdx.x & 63) == 0) {
         gu8 *v = (gu8 *)(a.out + ECX_CHECK_VERDICT(s) * a.out_stripe_stride);
         *v = 0;
     }
+#endif

@@ -21,6 +21,7 @@
 #include "engine.hpp"
 #include "host_pipe.hpp"
 #include "layout_probe.hpp"  // note_device_launch
+#include "locate.hpp"
 #include "pattern_set.hpp"
 #include "tune_table.hpp"
 #include "../../include/ecx_tune.h"
@@ -34,7 +35,7 @@ struct ecx_map {
 
 // What one of a codec's maps was built for.
 struct MapKey {
-    enum What { encode, check, decode, decode_partial, encode_partial, coding, helper_plane };
+    enum What { encode, check, decode, decode_partial, encode_partial, coding, helper_plane, locate };
     MapKey(What w, const std::vector<bool> &p = {}, int i = -1, int h = -1)
         : what(w), present(p.begin(), p.end()), index(i), helper(h) {}
     What what;
@@ -46,11 +47,13 @@ struct MapKey {
     }
 };
 using MapMemo = Memo<MapKey, ecx_map>;  // plans live as long as the codec
+using LocateMemo = Memo<MapKey, LocateSet>;  // the locate plan (locate_plan.hpp), beside the check map
 
 struct ecx_rs {
     explicit ecx_rs(int k, int m) : code(k, m) {}
     RsCode code;
     MapMemo maps;
+    LocateMemo locates;
 };
 
 // A pattern set (ecx.h): the decode maps of its patterns as one device plan.  `rs` is a reference
@@ -166,6 +169,28 @@ ecx_map *rs_check_plan(ecx_rs *rs) {
     return rs->maps.get({MapKey::check}, [&] { return rs_check_map(rs->code); });
 }
 
+// The locate plan of a codec (2 <= m <= 8), built once beside its check map.
+LocateSet *rs_locate_plan(ecx_rs *rs) {
+    return rs->locates.get({MapKey::locate}, [&] {
+        const RsCode &c = rs->code;
+        std::vector<uint8_t> parity;
+        for (int p = 0; p < c.m(); ++p) parity.insert(parity.end(), c.parity_row(p), c.parity_row(p) + c.k());
+        LocatePlan plan;
+        if (!build_locate_plan(parity.data(), c.k(), c.m(), &plan))
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "no locate plan for this code");
+        return plan;
+    });
+}
+
+// What both locate entry points refuse about the codec and the outputs it was asked for.
+void check_locatable(const ecx_rs *rs, const uint8_t *heal_id) {
+    const int m = rs->code.m();
+    if (m < 2) throw Error(ECX_E_ILLEGAL_ARGUMENT, "locate needs m >= 2: with one syndrome every shard explains it");
+    if (m > kLocateMaxParity)
+        throw Error(ECX_E_ILLEGAL_ARGUMENT, "locate takes m <= " + std::to_string(kLocateMaxParity) + " (one check tile)");
+    if (heal_id && rs->code.n() > 255) throw Error(ECX_E_ILLEGAL_ARGUMENT, "heal ids are bytes: n must be <= 255");
+}
+
 ecx_map *clay_coding_map(ecx_clay *c, const std::vector<bool> &present) {
     return c->maps.get({MapKey::coding, present}, [&] { return c->pl.perform_coding_map(present); });
 }
@@ -217,7 +242,7 @@ const char *ecx_status_string(int s) {
 }
 
 const char *ecx_last_error(void) { return g_last_error.c_str(); }
-int ecx_version(void) { return 107; }  // 1.07: 1.06 (check batches device and host, multi-GPU host batches, per-call executor) + pattern sets
+int ecx_version(void) { return 108; }  // 1.08: 1.07 (1.06 + pattern sets) + the corrupt-shard locate
 
 // ---------------------------------------------------------------- device
 int ecx_device_count(int *count) {
@@ -735,6 +760,21 @@ int ecx_rs_is_parity_correct_batch(ecx_rs *rs, const uint8_t *base, int64_t stri
         if (!base || !verdict) throw Error(ECX_E_NULL, "null device pointer");
         launch_check(rs_check_plan(rs)->cm, base + offset, stripe_stride, shard_stride, verdict, nstripes, byte_count,
                      (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+
+int ecx_rs_locate_corrupt_batch(ecx_rs *rs, const uint8_t *base, int64_t stripe_stride, int64_t shard_stride,
+                                int64_t nstripes, int64_t offset, int64_t byte_count, uint8_t *suspect,
+                                int32_t *culprit, uint8_t *heal_id, void *stream) {
+    return guarded(__func__, [&]() -> int {
+        if (!rs) throw Error(ECX_E_NULL, "null codec");
+        if (nstripes < 0 || offset < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        check_locatable(rs, heal_id);
+        if (nstripes == 0) return ECX_OK;
+        if (!base || !suspect || !culprit) throw Error(ECX_E_NULL, "null device pointer");
+        launch_locate(rs_check_plan(rs)->cm, *rs_locate_plan(rs), base + offset, stripe_stride, shard_stride, suspect,
+                      culprit, heal_id, nstripes, byte_count, (hipStream_t)stream);
         return ECX_OK;
     });
 }
@@ -1385,6 +1425,22 @@ int ecx_rs_is_parity_correct_blocked_batch(ecx_rs *rs, const uint8_t *base, int6
         if (!base || !verdict) throw Error(ECX_E_NULL, "null device pointer");
         launch_check_blocked(rs_check_plan(rs)->cm, base, rs->code.n(), nstripes, byte_count, block, verdict,
                              (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+
+int ecx_rs_locate_corrupt_blocked_batch(ecx_rs *rs, const uint8_t *base, int64_t nstripes, int64_t byte_count,
+                                        int64_t block_bytes, uint8_t *suspect, int32_t *culprit, uint8_t *heal_id,
+                                        void *stream) {
+    return guarded(__func__, [&]() -> int {
+        if (!rs) throw Error(ECX_E_NULL, "null codec");
+        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        const int64_t block = resolve_block(rs->code.n(), byte_count, block_bytes);
+        check_locatable(rs, heal_id);
+        if (nstripes == 0) return ECX_OK;
+        if (!base || !suspect || !culprit) throw Error(ECX_E_NULL, "null device pointer");
+        launch_locate_blocked(rs_check_plan(rs)->cm, *rs_locate_plan(rs), base, rs->code.n(), nstripes, byte_count,
+                              block, suspect, culprit, heal_id, (hipStream_t)stream);
         return ECX_OK;
     });
 }
