@@ -2994,8 +2994,9 @@ def test_launch_plan_names_what_runs(ecx, torch_dev):
     every kernel family of the product library -- k_gf_apply on 256 threads and on one wave, its
     small-row, LDS-table, depth-2 and deep-ring instances, k_gf_apply_tail, the wide tiles, the
     skewed chunks and k_map_planes -- ecx.last_launch_shape() after the real launch equals the
-    plan, and the output equals the default shape's.  Three stripes of at most 64 KiB shards,
-    and one stripe at a 4 MiB pitch (the skew's auto rule).  The lab kernels:
+    plan, and the output equals the default shape's.  Three stripes of at most 64 KiB shards
+    (five under xcd_group=3: 80 workgroups, past the 64 of one round of 8 XCDs x xcd_run, so the
+    reordered branch of logical_block runs), and one stripe at a 4 MiB pitch (the skew's auto rule).  The lab kernels:
     test_launch_plan_names_what_runs_diag."""
     cases = [
         ("rs124_dec01", 8208, "r16", 3, 0, 0, ""), ("rs124_dec01", 65536, "r16", 3, 1, 0, ""),
@@ -3013,7 +3014,7 @@ def test_launch_plan_names_what_runs(ecx, torch_dev):
         ("clay42_enc45", 65536, "r16", 3, 0, 0, "lds_tables=0"), ("rs173_enc", 8208, "r16", 3, 1, 0, "block_threads=64"),
         ("rs124_dec01", 8208, "r16", 3, 1, 0, "block_threads=256"), ("rs173_enc", 65536, "r16", 3, 1, 0, "skew_chunks=2"),
         ("rs124_dec01", 65536, "r16", 3, 1, 0, "block_threads=256,skew_chunks=4"), ("clay42_rep1", 65536, "r16", 3, 0, 0, "skew_chunks=2"),
-        ("rs173_enc", 8208, "r16", 3, 1, 0, "skew_chunks=2"), ("rs173_enc", 65536, "r16", 3, 1, 0, "xcd_group=3"),
+        ("rs173_enc", 8208, "r16", 3, 1, 0, "skew_chunks=2"), ("rs173_enc", 65536, "r16", 5, 1, 0, "xcd_group=3"),
         ("rs124_dec01", 65536, "r16", 3, 1, 0, "stagger=2"), ("rs173_enc", 65536, "r16", 3, 1, 0, "chunk_major=1"),
         ("clay42_rep03", 65536, "r16", 3, 0, 0, "map_planes=2"), ("rs173_enc", 8208, "r16", 3, 1, 1, "map_planes=2"),
     ]

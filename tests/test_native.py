@@ -95,3 +95,41 @@ def test_layout_selection_rules_and_recorded_trace_under_asan_ubsan(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     assert "layout_select_check: ok" in r.stdout
     assert f"{len(trace.read_text().splitlines())} trace lines replayed" in r.stdout
+
+
+UNIT_ORDER_BEGIN = "// Logical work index of this workgroup"
+UNIT_ORDER_END = "// One output tile over the workgroup's"
+
+
+def unit_order_slice(apply_hpp: str) -> str:
+    """The text of logical_block and unit_of, comments included, as it stands in csrc/apply.hpp."""
+    a, b = apply_hpp.index(UNIT_ORDER_BEGIN), apply_hpp.index(UNIT_ORDER_END)
+    text = apply_hpp[a:b]
+    assert a < b and text.count("__device__ __forceinline__") == 2, "apply.hpp: logical_block / unit_of moved"
+    assert "uint32_t logical_block(int xcd_group, uint32_t n_tiles, uint32_t run)" in text
+    assert "void unit_of(uint32_t u, uint32_t nc, uint32_t nst, int chunk_major, uint32_t G," in text
+    return text
+
+
+@pytest.mark.timeout(300)
+def test_unit_orders_are_bijections_under_asan_ubsan(tmp_path):
+    """Which (stripe, chunk, tile) a workgroup of the composed-map kernels computes (csrc/apply.hpp
+    logical_block and unit_of) is decided from blockIdx.x and gridDim.x inside the device functions.
+    Their text is cut out of apply.hpp unchanged and compiled on the host by
+    tests/native/unit_order_check.cpp, with blockIdx / gridDim as variables the check sets: it walks
+    every grid size 1..4096 the launcher can produce over 1, 2, 3, 5 and 32 tiles, every xcd_group,
+    xcd_run 1 / 3 / 8 / 4096, 1..9 chunks, the staggers and chunk_major, and asserts that the
+    workgroups hit every (tile, stripe, chunk) exactly once -- a mapping that does not leaves stale
+    bytes in the output."""
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "unit_order_check"
+    (tmp_path / "unit_order_slice.inc").write_text(
+        unit_order_slice((ROOT / "repair-pipelining_amd" / "csrc" / "apply.hpp").read_text()))
+    subprocess.run([gxx, "-std=c++17", "-O2", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-omit-frame-pointer", "-fno-sanitize-recover=all", "-I", str(tmp_path), "-o", str(exe),
+                    str(ROOT / "tests" / "native" / "unit_order_check.cpp")], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "unit_order_check: ok" in r.stdout
