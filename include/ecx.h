@@ -439,9 +439,18 @@ int ecx_clay_perform_coding_batch(ecx_clay *clay, const uint8_t *in, int64_t in_
  * An empty list is the "nothing erased" pattern and does nothing; duplicate lists are allowed.
  * The set holds one codec reference per distinct list and drops them in destroy.
  * Refused: npatterns outside 1..256 (ECX_E_ILLEGAL_ARGUMENT); a list the single step refuses (that
- * step's own status); a list whose map has more than 64 rows (ECX_E_ILLEGAL_ARGUMENT) -- the
- * geometries with 256 rows per node, Clay(10,4) and Clay(12,4), are left out: repair such stripes
- * with ecx_clay_perform_coding_batch, one list per call. */
+ * step's own status).
+ * A GENERATED set: the geometries with 256 rows per node, Clay(12,4) and the shortened Clay(10,4),
+ * have maps too tall for the device plan (more than 64 rows).  A set whose non-empty lists are all
+ * single nodes of such a geometry with q = 4 and t >= 3 is accepted and runs on a kernel generated
+ * for the set and compiled at run time with hiprtc (k_clay_repair_set: one straight-line body per
+ * distinct list, chosen per stripe by its id byte).  The first batch of such a set on a device
+ * compiles and loads it (a few tenths of a second per body) and must run outside stream capture; without hiprtc
+ * that batch returns ECX_E_DEVICE with the reason -- no other kernel can run these maps.
+ * Still refused with ECX_E_ILLEGAL_ARGUMENT, naming the list, its row count and
+ * ecx_clay_perform_coding_batch (repair such stripes with it, one list per call): a list of more
+ * than 64 rows that erases several nodes; a single-node list of more than 64 rows of a geometry
+ * without that kernel (Clay(9,3): 81 rows, q = 3); generated and plan lists mixed in one set. */
 typedef struct ecx_clay_pattern_set ecx_clay_pattern_set;
 int ecx_clay_pattern_set_create(int data_units, int parity_units, int virtual_units,
                                 const int *erased /* the lists back to back */,
@@ -463,7 +472,13 @@ int ecx_clay_pattern_set_info(const ecx_clay_pattern_set *set, int *npatterns, i
  * only enqueues.  Checked in this order: a null set (ECX_E_NULL); negative nstripes or buf_size
  * (ECX_E_ILLEGAL_ARGUMENT); nstripes == 0, buf_size == 0 or a set whose lists are all empty
  * (ECX_OK: no buffer is looked at, no device needed); a null pointer among the three (ECX_E_NULL);
- * a negative stride or an extent beyond int64_t (ECX_E_ILLEGAL_ARGUMENT). */
+ * a negative stride or an extent beyond int64_t (ECX_E_ILLEGAL_ARGUMENT).
+ * A generated set (above) covers whole 4 KiB chunks of 16-byte-aligned layouts and has no kernel
+ * for a tail, so after the checks above and before any device work it also refuses, with
+ * ECX_E_ILLEGAL_ARGUMENT and the offending value in the message: a buf_size that is not a multiple
+ * of 4096; a base or a stride that is not a multiple of 16 (Clay(10,4)'s sub-chunks are 4 KiB or
+ * 1 MiB; slot offsets beyond 31 bits take the kernel's 64-bit-address form).  The host form
+ * below stages every slot itself and has the buf_size rule only. */
 int ecx_clay_perform_coding_batch_mixed(const ecx_clay_pattern_set *set,
                                         const uint8_t *pattern_of_stripe /* device */, const uint8_t *in,
                                         int64_t in_stripe_stride, int64_t in_sub_stride, uint8_t *out,
@@ -495,7 +510,8 @@ int ecx_clay_perform_coding_batch_mixed(const ecx_clay_pattern_set *set,
  * order: null set ECX_E_NULL; negative nstripes or buf_size ECX_E_ILLEGAL_ARGUMENT; nstripes == 0,
  * buf_size == 0 or a set whose lists are all empty ECX_OK (no buffers, no device); a null pointer
  * among the four ECX_E_NULL; a negative stride or an extent beyond int64_t
- * ECX_E_ILLEGAL_ARGUMENT. */
+ * ECX_E_ILLEGAL_ARGUMENT.  A generated set (ecx_clay_pattern_set_create) has no partial-sum hop
+ * yet: it is refused by name (ECX_E_ILLEGAL_ARGUMENT) right after the null-set check. */
 int ecx_clay_partial_batch_mixed(const ecx_clay_pattern_set *set,
                                  const uint8_t *pattern_of_stripe /* device */,
                                  const uint8_t *node_of_stripe /* device */, const uint8_t *in,
@@ -563,7 +579,11 @@ int ecx_clay_perform_coding_batch_host_devices(ecx_clay *clay, const uint8_t *in
  * them for a stripe whose id has no list or whose list is empty.  This is the one place where the
  * host form differs from the device form, which leaves those bytes untouched.  Host bytes outside
  * the returned slots and outside [0, buf_size) of a slot are untouched.  The checks and their
- * order are the device form's.  There is no _host_devices form. */
+ * order are the device form's.  There is no _host_devices form.  A generated set
+ * (ecx_clay_pattern_set_create) runs the same ring with k_clay_repair_set as its launch: the union
+ * of its lists' helper planes goes up (all 3,584 slots of a stripe for the 14 single-node lists of
+ * Clay(10,4)), slots 0 .. alpha - 1 come back, the zero rule is unchanged, and buf_size must be a
+ * multiple of 4096 (the staging buffers give the alignment the kernel needs). */
 int ecx_clay_perform_coding_mixed_batch_host(const ecx_clay_pattern_set *set,
                                              const uint8_t *pattern_of_stripe /* host */, const uint8_t *in,
                                              int64_t in_stripe_stride, int64_t in_sub_stride, uint8_t *out,

@@ -259,6 +259,21 @@ int ecx_clay_rtc_compile_check(struct ecx_clay *clay);
 /* The generated kernel source: copied NUL-terminated into buf when len exceeds its
  * length; returns the length. */
 int ecx_clay_rtc_source(struct ecx_clay *clay, char *buf, int len);
+/* The generated set kernel k_clay_repair_set of a generated Clay pattern set (ecx.h
+ * ecx_clay_pattern_set: single-node lists of maps of more than 64 rows) has four exports of the
+ * same kind, for tests and measurement scripts.  They are exported by the library but prototyped
+ * here in this comment only -- a caller declares the one it uses:
+ *   int ecx_clay_pattern_set_generated(const struct ecx_clay_pattern_set *set);
+ *   int ecx_clay_pattern_set_rtc_source(const struct ecx_clay_pattern_set *set, char *buf, int len);
+ *   int ecx_clay_pattern_set_rtc_compile_check(const struct ecx_clay_pattern_set *set);
+ *   int ecx_clay_pattern_set_rtc_resources(const struct ecx_clay_pattern_set *set, int *vgprs,
+ *                                          int *lds_bytes, int *scratch_bytes, int64_t *code_bytes);
+ * _generated returns 1 for such a set and 0 for a composed one; the others return
+ * ECX_E_ILLEGAL_ARGUMENT for a composed set.  _rtc_source and _rtc_compile_check are
+ * ecx_clay_rtc_source's and ecx_clay_rtc_compile_check's twins at the current shape knobs (no
+ * device needed).  _rtc_resources compiles and loads the kernel on the current device when it is
+ * not yet, and reports its registers, static LDS bytes and scratch bytes (hipFuncGetAttribute) and
+ * its code object's size; any out pointer may be null. */
 /* The bit-plane kernel of a composed map (ecx_tune "map_planes"), overwriting or, with
  * accumulate != 0, XOR-accumulating its outputs: compile it with hiprtc for gfx950 (no
  * device needed) and return the code-object size, or copy its source NUL-terminated into

@@ -6,8 +6,11 @@ package com.backblaze.erasure.ecx;
  * batch are compiled once into a pattern set, and each stripe names its list with one byte.
  * Stripe s holds n*alpha sub-chunks (slot z*n + node) and receives the |E|*alpha sub-chunks of its
  * own list (slot z*|E| + j).  A stripe whose list is empty, or whose id names no list, is left
- * untouched by the device form and gets zeros from the host form.  Lists of more than 64 rows
- * (Clay(10,4), Clay(12,4)) are refused: repair those with EcxClayCodeErasureDecodingStep.
+ * untouched by the device form and gets zeros from the host form.  Single-node lists of the
+ * geometries with 256 rows per node (Clay(12,4), the shortened Clay(10,4)) form a generated set:
+ * its kernel is generated and compiled on the first repair, and it takes sub-chunk sizes that are
+ * multiples of 4096 in 16-byte-aligned layouts only.  Lists of more than 64 rows that erase
+ * several nodes are refused: repair those with EcxClayCodeErasureDecodingStep.
  * The set must stay open until the work enqueued with it has finished; the first repair on a
  * device must run outside stream capture.
  */

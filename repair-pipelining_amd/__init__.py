@@ -1239,6 +1239,44 @@ class ClayPatternSet:
         keys = ("slots_up", "slots_down", "chunk", "chunks", "buffers", "h2d_copies", "d2h_copies")
         return {k: int(v) for k, v in zip(keys, out)}
 
+    def _diag(self, name, argtypes):
+        """A diagnostic export beside ecx_clay_rtc_source (include/ecx_tune.h), bound on use."""
+        if self._h is None:
+            raise EcxError(-6, "the pattern set is closed")
+        f = getattr(lib(), name)
+        f.argtypes, f.restype = [ctypes.c_void_p] + argtypes, ctypes.c_int
+        return f
+
+    @property
+    def generated(self) -> bool:
+        """True for a generated set: single-node lists of maps of more than 64 rows (Clay(12,4),
+        the shortened Clay(10,4)), run by the generated kernel k_clay_repair_set."""
+        return check(self._diag("ecx_clay_pattern_set_generated", [])(self._h)) == 1
+
+    def rtcSource(self) -> str:
+        """The generated k_clay_repair_set source at the current shape knobs
+        (ecx_clay_pattern_set_rtc_source); an EcxError for a composed set."""
+        f = self._diag("ecx_clay_pattern_set_rtc_source", [ctypes.c_char_p, ctypes.c_int])
+        n = check(f(self._h, None, 0))
+        buf = ctypes.create_string_buffer(n + 1)
+        check(f(self._h, buf, n + 1))
+        return buf.value.decode()
+
+    def rtcCompileCheck(self) -> int:
+        """Compile the set kernel with hiprtc for gfx950 (no device needed); returns the
+        code-object size (ecx_clay_pattern_set_rtc_compile_check)."""
+        return check(self._diag("ecx_clay_pattern_set_rtc_compile_check", [])(self._h))
+
+    def rtcResources(self):
+        """The loaded set kernel's resources on the current device, a dict of vgprs, lds_bytes,
+        scratch_bytes (hipFuncGetAttribute) and code_bytes (the code object's size); compiles and
+        loads the kernel when it is not yet (ecx_clay_pattern_set_rtc_resources)."""
+        v, code = [ctypes.c_int() for _ in range(3)], ctypes.c_int64()
+        f = self._diag("ecx_clay_pattern_set_rtc_resources",
+                       [ctypes.POINTER(ctypes.c_int)] * 3 + [ctypes.POINTER(ctypes.c_int64)])
+        check(f(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(code)))
+        return {"vgprs": v[0].value, "lds_bytes": v[1].value, "scratch_bytes": v[2].value, "code_bytes": code.value}
+
     def _check_batch(self, inp, iss, isl, out, oss, osl, nstripes, nbytes):
         if self._h is None:
             raise EcxError(-6, "the pattern set is closed")
@@ -1284,6 +1322,7 @@ class ClayPatternSet:
         list's own.  Only enqueues."""
         if self._h is None:
             raise EcxError(-6, "the pattern set is closed")
+        self.refusePartial()
         if self.maxErased != 0 and nstripes > 0 and bufSize > 0:
             if in_node_stride < 0:
                 raise EcxError(-1, "input: negative stride")
@@ -1297,6 +1336,12 @@ class ClayPatternSet:
                                                  in_stripe_stride, in_node_stride, in_sub_stride, _dev_ptr(acc),
                                                  acc_stripe_stride, acc_sub_stride, nstripes, bufSize,
                                                  1 if is_first else 0, _stream(stream)))
+
+    def refusePartial(self) -> None:
+        """A generated set has no partial-sum hop yet: raises the library's own refusal
+        (ecx_clay_partial_batch_mixed, before any device work); nothing for a composed set."""
+        if self.generated:
+            check(lib().ecx_clay_partial_batch_mixed(self._h, None, None, None, 0, 0, 0, None, 0, 0, 0, 0, 0, None))
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None:

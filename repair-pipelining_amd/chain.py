@@ -321,6 +321,10 @@ class ClayPatternChain(RepairChain):
         self.rank, self.order, self.group = rank, list(order), group
         self.dest = self.order[-1] if dest is None else dest
         self._place_on_chain()
+        # a generated set (k_clay_repair_set) has no partial-sum hop yet: the library's refusal
+        refuse = getattr(pattern_set, "refusePartial", None)
+        if refuse is not None:
+            refuse()
         self.partial = (partial_factory or _ClaySetPartial)(pattern_set)
         self.alpha = int(self.partial.alpha)
         self.n_out_slots = int(self.partial.max_erased) * self.alpha

@@ -97,6 +97,50 @@ private:
     std::unique_ptr<Impl> impl_;
 };
 
+// The set kernel `k_clay_repair_set`: k_clay_repair_grp with the erased node chosen per stripe by
+// a byte of `ids`.  `programs` are the single-node repair programs of one geometry (all
+// clay_grp_supported), `id_to_body[id]` the program of id, -1 for an id without a list or with
+// the empty list: such a stripe's workgroups end before any load or store.  The geometry-only
+// part of k_clay_repair_grp's source is emitted once, then one straight-line body per program as
+// a case of a switch on the wave-uniform id; the bodies share the one LDS exchange buffer.
+// rtc_units 2, rtc_persist and the diagnostic forms are refused (ECX_E_ILLEGAL_ARGUMENT).
+std::string clay_set_source(const std::vector<ClayRepairProgram> &programs, const int (&id_to_body)[256],
+                            const RtcShape &shape = RtcShape());
+
+class ClaySetRtc {
+public:
+    ClaySetRtc(std::vector<ClayRepairProgram> programs, const int (&id_to_body)[256]);
+    ~ClaySetRtc();
+    const std::vector<ClayRepairProgram> &programs() const { return programs_; }
+    std::string source(const RtcShape &shape) const;
+    // The largest input slot any body reads, the union of the slots the bodies read and the
+    // output slots 0 .. alpha-1 (sorted): what a host batch moves.
+    int max_in_slot() const { return max_in_slot_; }
+    const std::vector<int> &in_slots() const { return in_slots_; }
+    const std::vector<int> &out_slots() const { return out_slots_; }
+    // Compile and load as ClayRtc::available: once per (source, device), deterministic failures
+    // remembered, a first use under capture refused (thrown).
+    bool available(const RtcShape &shape, std::string *why = nullptr);
+    // One launch (split at 2^30 workgroups) over nstripes stripes in the performCoding batch
+    // layout; ids[s] is stripe s's id (a device array).  Throws ECX_E_DEVICE with the reason
+    // when the kernel cannot be compiled or loaded: there is no other kernel for these maps.
+    void launch(const RtcShape &shape, const uint8_t *ids, const uint8_t *in, int64_t in_stripe_stride,
+                int64_t in_slot_stride, uint8_t *out, int64_t out_stripe_stride, int64_t out_slot_stride,
+                int64_t nstripes, int64_t nchunks, hipStream_t stream);
+    // The loaded kernel's registers, static LDS and scratch bytes (hipFuncGetAttribute) and its
+    // code object's size; loads the kernel when it is not yet.
+    void resources(const RtcShape &shape, int *vgprs, int *lds_bytes, int *scratch_bytes, int64_t *code_bytes);
+
+    struct Impl;  // (public for clay_rtc.cpp's helper)
+
+private:
+    std::vector<ClayRepairProgram> programs_;
+    int id_to_body_[256];
+    int max_in_slot_ = -1;
+    std::vector<int> in_slots_, out_slots_;
+    std::unique_ptr<Impl> impl_;
+};
+
 // Compile `source` with hiprtc (diagnostics / tests: no device needed).
 // Returns the code object size, throws ECX_E_DEVICE with the compiler log on failure.
 size_t rtc_compile_check(const std::string &source);

@@ -1112,8 +1112,20 @@ struct ecx_clay_pattern_set {
     ecx_clay_pattern_set() : codecs(clay_registry()) {}
     RefBundle<ecx_clay, ClayKey> codecs;
     std::unique_ptr<PatternSet> set;  // destroyed in ~: before the references go (declared after them)
+    // A generated set (ecx.h): single-node lists of maps too tall for the composed plan, run by
+    // k_clay_repair_set (clay_rtc.hpp).  Exactly one of `set` and `gen` is there.
+    std::unique_ptr<ClaySetRtc> gen;
     int npatterns = 0, nodes = 0, alpha = 0, max_erased = 0;
+    int max_out_slot() const { return gen ? (gen->programs().empty() ? -1 : alpha - 1) : set->max_out_slot(); }
+    const std::vector<int> &in_slots() const { return gen ? gen->in_slots() : set->in_slots(); }
+    const std::vector<int> &out_slots() const { return gen ? gen->out_slots() : set->out_slots(); }
 };
+
+namespace {
+const char *const kGeneratedSetNoPartial =
+    "a generated pattern set (k_clay_repair_set) has no partial-sum hop: repair its stripes with "
+    "ecx_clay_perform_coding_batch_mixed";
+}  // namespace
 
 int ecx_clay_pattern_set_create(int data_units, int parity_units, int virtual_units, const int *erased,
                                 const int *n_erased, int npatterns, ecx_clay_pattern_set **out) {
@@ -1132,6 +1144,12 @@ int ecx_clay_pattern_set_create(int data_units, int parity_units, int virtual_un
         if (total > 0 && !erased) throw Error(ECX_E_NULL, "null erased lists");
         auto set = std::make_unique<ecx_clay_pattern_set>();
         std::vector<const CompiledMap *> maps;
+        // a generated set's bodies: one program per distinct node, and each id's body
+        std::vector<ClayRepairProgram> programs;
+        std::map<int, int> body_of_node;
+        int id_to_body[256];
+        std::fill(id_to_body, id_to_body + 256, -1);
+        int first_generated = -1, first_composed = -1;
         const int *list = erased;
         for (int p = 0; p < npatterns; list += n_erased[p], ++p) {
             const std::vector<int> e(list, list + n_erased[p]);  // order matters (the reference's erasedIndexes)
@@ -1140,20 +1158,44 @@ int ecx_clay_pattern_set_create(int data_units, int parity_units, int virtual_un
                 return new ecx_clay(data_units, parity_units, e, virtual_units, false);
             });
             const int rows = (int)e.size() * c->pl.alpha();
-            if (rows > kMixedMaxTiles * kTileRows) {
+            auto refuse = [&](const std::string &why) {
                 std::string names;
                 for (int x : e) names += (names.empty() ? "" : ",") + std::to_string(x);
                 throw Error(ECX_E_ILLEGAL_ARGUMENT,
                             "list " + std::to_string(p) + " {" + names + "} has a map of " + std::to_string(rows) +
-                                " rows, a pattern set takes at most " + std::to_string(kMixedMaxTiles * kTileRows) +
+                                " rows, a pattern set takes at most " + std::to_string(kMixedMaxTiles * kTileRows) + why +
                                 ": repair such stripes with ecx_clay_perform_coding_batch, one list per call");
-            }
-            maps.push_back(&clay_standard_map(c)->cm);
+            };
             set->nodes = c->pl.n_real();
             set->alpha = c->pl.alpha();
             set->max_erased = std::max(set->max_erased, (int)e.size());
+            if (rows > kMixedMaxTiles * kTileRows) {
+                // taller maps run on the generated set kernel, which has single-node bodies only
+                if (e.size() != 1) refuse(" (or single-node lists of a q = 4 geometry, on the generated set kernel)");
+                ClayRtc *r = clay_rtc(c);
+                std::string why = r ? std::string() : c->rtc_why;
+                if (!r || !clay_grp_supported(r->program(), &why))
+                    refuse(", and the generated set kernel needs q = 4 and t >= 3 (" + why + ")");
+                if (first_generated < 0) first_generated = p;
+                auto at = body_of_node.find(e[0]);
+                if (at == body_of_node.end()) {
+                    at = body_of_node.emplace(e[0], (int)programs.size()).first;
+                    programs.push_back(r->program());
+                }
+                id_to_body[p] = at->second;
+                continue;
+            }
+            if (!e.empty() && first_composed < 0) first_composed = p;
+            maps.push_back(&clay_standard_map(c)->cm);
         }
-        set->set = std::make_unique<PatternSet>(maps);
+        if (first_generated >= 0 && first_composed >= 0)
+            throw Error(ECX_E_ILLEGAL_ARGUMENT,
+                        "list " + std::to_string(first_generated) + " runs on the generated set kernel and list " +
+                            std::to_string(first_composed) + " on the composed-map kernel: a pattern set holds one kind");
+        if (first_generated >= 0)
+            set->gen = std::make_unique<ClaySetRtc>(std::move(programs), id_to_body);
+        else
+            set->set = std::make_unique<PatternSet>(maps);
         set->npatterns = npatterns;
         *out = set.release();
         return ECX_OK;
@@ -1163,6 +1205,7 @@ int ecx_clay_pattern_set_create(int data_units, int parity_units, int virtual_un
 void ecx_clay_pattern_set_destroy(ecx_clay_pattern_set *set) {
     if (!set) return;
     set->set.reset();  // the device plans first (hipFree), then the codec references
+    set->gen.reset();
     delete set;
 }
 
@@ -1186,22 +1229,62 @@ int clay_mixed_batch(const char *fn, const ecx_clay_pattern_set *set, const uint
     return guarded(fn, [&]() -> int {
         if (!set) throw Error(ECX_E_NULL, "null pattern set");
         if (nstripes < 0 || buf_size < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
-        if (nstripes == 0 || buf_size == 0 || set->set->max_out_slot() < 0) return ECX_OK;
+        if (nstripes == 0 || buf_size == 0 || set->max_out_slot() < 0) return ECX_OK;
         if (!pattern_of_stripe || !in || !out) throw Error(ECX_E_NULL, host ? "null host pointer" : "null device pointer");
         const int n_in = set->nodes * set->alpha;
         if (in_stripe_stride < 0 || in_sub_stride < 0 || out_stripe_stride < 0 || out_sub_stride < 0)
             throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative stride");
         if (!extent_fits({{nstripes, in_stripe_stride}, {(int64_t)n_in, in_sub_stride}}, buf_size) ||
-            !extent_fits({{nstripes, out_stripe_stride}, {(int64_t)set->set->max_out_slot() + 1, out_sub_stride}}, buf_size))
+            !extent_fits({{nstripes, out_stripe_stride}, {(int64_t)set->max_out_slot() + 1, out_sub_stride}}, buf_size))
             throw Error(ECX_E_ILLEGAL_ARGUMENT, "batch extent overflows");
-        PatternSet &ps = *set->set;
+        MapMixedRun run{set->in_slots(), set->out_slots(), nullptr};
+        if (ClaySetRtc *g = set->gen.get()) {
+            // k_clay_repair_set covers whole 4 KiB chunks of 16-B-aligned layouts, and nothing
+            // here can take a tail (the composed kernel cannot run these maps)
+            if (buf_size % kChunkBytes != 0)
+                throw Error(ECX_E_ILLEGAL_ARGUMENT, "a generated pattern set takes a buf_size that is a multiple of " +
+                                                        std::to_string(kChunkBytes) + ": " + std::to_string(buf_size));
+            if (!host) {
+                const std::pair<const char *, int64_t> aligned[] = {
+                    {"in", (int64_t)(uintptr_t)in},           {"out", (int64_t)(uintptr_t)out},
+                    {"in_stripe_stride", in_stripe_stride},   {"in_sub_stride", in_sub_stride},
+                    {"out_stripe_stride", out_stripe_stride}, {"out_sub_stride", out_sub_stride}};
+                for (const auto &a : aligned)
+                    if (a.second % 16 != 0)
+                        throw Error(ECX_E_ILLEGAL_ARGUMENT,
+                                    std::string("a generated pattern set takes bases and strides that are multiples of 16: ") +
+                                        a.first + " = " + std::to_string(a.second));
+            }
+            run.launch = [g](const uint8_t *ids, const uint8_t *pin, int64_t iss, int64_t isl, uint8_t *pout, int64_t oss,
+                             int64_t osl, int64_t units, int64_t nbytes, int64_t first_unit, hipStream_t s) {
+                RtcShape sh = rtc_current_shape();
+                // slot offsets beyond 31 bits: 64-bit load addresses, by ecx_clay_perform_coding_batch's rule
+                if ((int64_t)g->max_in_slot() * isl + kChunkBytes > 0x7FFFFFFF) sh.wide = 1;
+                g->launch(sh, ids + first_unit, pin, iss, isl, pout, oss, osl, units, nbytes / kChunkBytes, s);
+            };
+        } else {
+            PatternSet *ps = set->set.get();
+            run.launch = [ps](const uint8_t *ids, const uint8_t *pin, int64_t iss, int64_t isl, uint8_t *pout,
+                              int64_t oss, int64_t osl, int64_t units, int64_t nbytes, int64_t first_unit, hipStream_t s) {
+                launch_map_mixed(*ps, ids, pin, iss, isl, pout, oss, osl, units, nbytes, first_unit, s);
+            };
+        }
         if (host) {
             const HostMixedIds ids(pattern_of_stripe, nstripes);
-            run_host_map_mixed_batch(ps, ids.get(), in, in_stripe_stride, in_sub_stride, n_in, out, out_stripe_stride,
+            run_host_map_mixed_batch(run, ids.get(), in, in_stripe_stride, in_sub_stride, n_in, out, out_stripe_stride,
                                      out_sub_stride, nstripes, buf_size);
+        } else if (set->gen) {
+            // first use of the module or the zero page is refused under capture (engine.hpp)
+            const LaunchStreamScope scope((hipStream_t)stream);
+            run.launch(pattern_of_stripe, in, in_stripe_stride, in_sub_stride, out, out_stripe_stride, out_sub_stride,
+                       nstripes, buf_size, 0, (hipStream_t)stream);
+            int dev = 0;
+            check_hip(hipGetDevice(&dev), "hipGetDevice");
+            note_device_launch(dev, (hipStream_t)stream, nstripes * buf_size * (int64_t)(set->gen->max_in_slot() + 1));
+            set_last_kernel("k_clay_repair_set");
         } else {
-            launch_map_mixed(ps, pattern_of_stripe, in, in_stripe_stride, in_sub_stride, out, out_stripe_stride,
-                             out_sub_stride, nstripes, buf_size, 0, (hipStream_t)stream);
+            run.launch(pattern_of_stripe, in, in_stripe_stride, in_sub_stride, out, out_stripe_stride, out_sub_stride,
+                       nstripes, buf_size, 0, (hipStream_t)stream);
         }
         return ECX_OK;
     });
@@ -1232,6 +1315,7 @@ int ecx_clay_partial_batch_mixed(const ecx_clay_pattern_set *set, const uint8_t 
                                  int is_first, void *stream) {
     return guarded(__func__, [&]() -> int {
         if (!set) throw Error(ECX_E_NULL, "null pattern set");
+        if (set->gen) throw Error(ECX_E_ILLEGAL_ARGUMENT, kGeneratedSetNoPartial);
         if (nstripes < 0 || buf_size < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
         if (nstripes == 0 || buf_size == 0 || set->set->max_out_slot() < 0) return ECX_OK;
         if (!pattern_of_stripe || !node_of_stripe || !in || !acc) throw Error(ECX_E_NULL, "null device pointer");
@@ -1262,6 +1346,50 @@ int ecx_clay_rtc_source(ecx_clay *clay, char *buf, int len) {
         const std::string src = clay_rtc_selected_source(r->program(), rtc_current_shape());
         if (buf && len > (int)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
         return (int)src.size();
+    });
+}
+
+namespace {
+ClaySetRtc &generated_of(const ecx_clay_pattern_set *set) {
+    if (!set) throw Error(ECX_E_NULL, "null pattern set");
+    if (!set->gen) throw Error(ECX_E_ILLEGAL_ARGUMENT, "not a generated pattern set: its lists run on the composed-map kernel");
+    return *set->gen;
+}
+}  // namespace
+
+// Diagnostic exports of a generated set (prototyped in a comment of include/ecx_tune.h)
+extern "C" {
+int ecx_clay_pattern_set_generated(const ecx_clay_pattern_set *set);
+int ecx_clay_pattern_set_rtc_source(const ecx_clay_pattern_set *set, char *buf, int len);
+int ecx_clay_pattern_set_rtc_compile_check(const ecx_clay_pattern_set *set);
+int ecx_clay_pattern_set_rtc_resources(const ecx_clay_pattern_set *set, int *vgprs, int *lds_bytes, int *scratch_bytes,
+                                       int64_t *code_bytes);
+}
+
+int ecx_clay_pattern_set_generated(const ecx_clay_pattern_set *set) {
+    if (!set) return ECX_E_NULL;
+    return set->gen ? 1 : 0;
+}
+
+int ecx_clay_pattern_set_rtc_source(const ecx_clay_pattern_set *set, char *buf, int len) {
+    return guarded(__func__, [&]() -> int {
+        const std::string src = generated_of(set).source(rtc_current_shape());
+        if (buf && len > (int)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
+        return (int)src.size();
+    });
+}
+
+int ecx_clay_pattern_set_rtc_compile_check(const ecx_clay_pattern_set *set) {
+    return guarded(__func__, [&]() -> int {
+        return (int)rtc_compile_check(generated_of(set).source(rtc_current_shape()));
+    });
+}
+
+int ecx_clay_pattern_set_rtc_resources(const ecx_clay_pattern_set *set, int *vgprs, int *lds_bytes, int *scratch_bytes,
+                                       int64_t *code_bytes) {
+    return guarded(__func__, [&]() -> int {
+        generated_of(set).resources(rtc_current_shape(), vgprs, lds_bytes, scratch_bytes, code_bytes);
+        return ECX_OK;
     });
 }
 
@@ -1640,13 +1768,13 @@ int ecx_clay_pattern_set_host_plan(const ecx_clay_pattern_set *set, int64_t in_s
         if (!set || !plan) throw Error(ECX_E_NULL, "null pattern set or plan");
         if (nstripes < 0 || buf_size < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
         int64_t v[7] = {0, 0, 0, 0, 0, 0, 0};
-        const PatternSet &ps = *set->set;
-        if (nstripes > 0 && buf_size > 0 && ps.max_out_slot() >= 0) {
+        if (nstripes > 0 && buf_size > 0 && set->max_out_slot() >= 0) {
             const Tuning t = tuning();
             const HostMapMixedPlan mp = make_map_mixed_plan(
-                ps.in_slots(), ps.out_slots(), in_stripe_stride, in_sub_stride, set->nodes * set->alpha, out_stripe_stride,
-                out_sub_stride, ps.max_out_slot() + 1, nstripes, buf_size, t.host_chunk, t.host_buffers);
-            const int64_t w[7] = {(int64_t)ps.in_slots().size(), (int64_t)ps.out_slots().size(), mp.chunk, mp.nchunks,
+                set->in_slots(), set->out_slots(), in_stripe_stride, in_sub_stride, set->nodes * set->alpha,
+                out_stripe_stride, out_sub_stride, set->max_out_slot() + 1, nstripes, buf_size, t.host_chunk,
+                t.host_buffers);
+            const int64_t w[7] = {(int64_t)set->in_slots().size(), (int64_t)set->out_slots().size(), mp.chunk, mp.nchunks,
                                   mp.nb, (int64_t)mp.cin.size(), (int64_t)mp.cout.size()};
             std::memcpy(v, w, sizeof(v));
         }

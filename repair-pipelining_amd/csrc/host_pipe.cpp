@@ -366,13 +366,13 @@ void run_host_mixed_batch(PatternSet &set, const uint8_t *dev_ids, uint8_t *base
 // slot (make_map_mixed_plan).  The launch writes only what a stripe's own pattern writes, and every
 // output slot of every stripe goes back, so the chunk's output area is cleared on the compute
 // stream first -- after the ring's wait for the earlier unit's D2H, before the launch.
-void run_host_map_mixed_batch(PatternSet &set, const uint8_t *dev_ids, const uint8_t *in, int64_t in_stripe_stride,
-                              int64_t in_slot_stride, int n_in, uint8_t *out, int64_t out_stripe_stride,
-                              int64_t out_slot_stride, int64_t nstripes, int64_t nbytes) {
-    if (nstripes <= 0 || nbytes <= 0 || set.out_slots().empty()) return;
+void run_host_map_mixed_batch(const MapMixedRun &run, const uint8_t *dev_ids, const uint8_t *in,
+                              int64_t in_stripe_stride, int64_t in_slot_stride, int n_in, uint8_t *out,
+                              int64_t out_stripe_stride, int64_t out_slot_stride, int64_t nstripes, int64_t nbytes) {
+    if (nstripes <= 0 || nbytes <= 0 || run.out_slots.empty()) return;
     const Tuning &t = tuning();
-    const int n_out = set.max_out_slot() + 1;
-    const HostMapMixedPlan mp = make_map_mixed_plan(set.in_slots(), set.out_slots(), in_stripe_stride, in_slot_stride,
+    const int n_out = (int)run.out_slots.size();
+    const HostMapMixedPlan mp = make_map_mixed_plan(run.in_slots, run.out_slots, in_stripe_stride, in_slot_stride,
                                                     n_in, out_stripe_stride, out_slot_stride, n_out, nstripes, nbytes,
                                                     t.host_chunk, t.host_buffers);
     const int64_t chunk = mp.chunk;
@@ -387,8 +387,7 @@ void run_host_map_mixed_batch(PatternSet &set, const uint8_t *dev_ids, const uin
         },
         [&](int64_t i, HostPipe::Set &b, hipStream_t s) {
             check_hip(hipMemsetAsync(b.out, 0, (size_t)(count(i) * mp.out_per), s), "hipMemsetAsync (host map mixed batch)");
-            launch_map_mixed(set, dev_ids, b.in, mp.in_per, nbytes, b.out, mp.out_per, nbytes, count(i), nbytes,
-                             i * chunk, s);
+            run.launch(dev_ids, b.in, mp.in_per, nbytes, b.out, mp.out_per, nbytes, count(i), nbytes, i * chunk, s);
         },
         [&](int64_t i, HostPipe::Set &b, hipStream_t s) {
             for (const Copy &c : mp.cout)

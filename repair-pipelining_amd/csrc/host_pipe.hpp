@@ -6,6 +6,8 @@
 // (profiles/pmc_traffic.json), so its text moves only together with a new profile.
 #pragma once
 
+#include <functional>
+
 #include "engine.hpp"
 #include "host_plan.hpp"
 
@@ -33,14 +35,26 @@ void run_host_check_batch_devices(CompiledMap &cm, const uint8_t *in, int64_t in
 // units go H2D (up_slots), through launch_apply_mixed_units, and D2H (down_slots).
 void run_host_mixed_batch(PatternSet &set, const uint8_t *dev_ids, uint8_t *base, int64_t stripe_stride,
                           int64_t slot_stride, int n, int64_t units, int64_t nbytes, int64_t divisor);
+// What the out-of-place ring needs of a set: the input slots that go up, the output slots
+// 0 .. n-1 that come back, and the launch over one chunk of stripes -- unit u of the chunk runs
+// the list ids[first_unit + u].  A composed set (PatternSet, launch_map_mixed) and a generated
+// one (ClaySetRtc, k_clay_repair_set) both fill it in.
+struct MapMixedRun {
+    const std::vector<int> &in_slots;
+    const std::vector<int> &out_slots;
+    std::function<void(const uint8_t *ids, const uint8_t *in, int64_t in_stripe_stride, int64_t in_slot_stride,
+                       uint8_t *out, int64_t out_stripe_stride, int64_t out_slot_stride, int64_t units, int64_t nbytes,
+                       int64_t first_unit, hipStream_t stream)>
+        launch;
+};
 // The out-of-place twin for a set of maps of several tiles (the Clay repair with a list per
 // stripe), synchronous, on the current device: `nstripes` stripes of n_in input slots at `in` and
-// max_out_slot() + 1 output slots at `out`, both in host memory.  Chunks of stripes go H2D
-// (in_slots), through launch_map_mixed into an output area cleared on the compute stream, and
+// out_slots.size() output slots at `out`, both in host memory.  Chunks of stripes go H2D
+// (in_slots), through run.launch into an output area cleared on the compute stream, and
 // D2H (out_slots): what a stripe's own pattern does not write comes back as zeros.
-void run_host_map_mixed_batch(PatternSet &set, const uint8_t *dev_ids, const uint8_t *in, int64_t in_stripe_stride,
-                              int64_t in_slot_stride, int n_in, uint8_t *out, int64_t out_stripe_stride,
-                              int64_t out_slot_stride, int64_t nstripes, int64_t nbytes);
+void run_host_map_mixed_batch(const MapMixedRun &run, const uint8_t *dev_ids, const uint8_t *in,
+                              int64_t in_stripe_stride, int64_t in_slot_stride, int n_in, uint8_t *out,
+                              int64_t out_stripe_stride, int64_t out_slot_stride, int64_t nstripes, int64_t nbytes);
 // The caller's host ids on the current device for the length of one host call (freed by the
 // destructor): they cross once per call, not once per chunk.
 class HostMixedIds {
