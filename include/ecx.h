@@ -266,6 +266,43 @@ int ecx_rs_locate_corrupt_blocked_batch(ecx_rs *rs, const uint8_t *base, int64_t
                                         int64_t block_bytes, uint8_t *suspect, int32_t *culprit, uint8_t *heal_id,
                                         void *stream);
 
+/* Which ONE OR TWO shards are corrupt?  ecx_rs_locate_corrupt_batch leaves a stripe with two corrupt
+ * shards at culprit -2; a code with m >= 4 parity shards has distance m + 1 >= 5 and corrects two
+ * errors.  Arguments and layout of ecx_rs_locate_corrupt_batch, read-only, with wider outputs:
+ *   suspect[s]    (a device byte array [nstripes][n + C(n,2)]): the n single suspects as above, then
+ *                 one byte per pair {i, j}, i < j, at n + p with p = i(2n - i - 1)/2 + (j - i - 1)
+ *                 (lexicographic pair order): 1 when replacing shards i and j together can make the
+ *                 stripe pass isParityCorrect, else 0;
+ *   culprit[s]    (a device int32 array [nstripes][2]) and heal_id[s] (device bytes, or NULL):
+ *                   all n singles set                        (-1, -1)   255
+ *                   exactly one single, j                    (j, -1)    j
+ *                   no single, exactly one pair p = {i, j}   (i, j)     n + p
+ *                   anything else                            (-2, -2)   255
+ * The pattern set of the n single-loss patterns in shard order followed by the C(n,2) pair-loss
+ * patterns in pair order gives every heal id its pattern, so ecx_rs_decode_missing_batch_mixed on
+ * the same stream heals the batch.  The pair {i, j} explains a stripe exactly when S(b) lies in
+ * span(H_i, H_j) at every b: m - 2 test rows per pair on the syndromes the check holds in
+ * registers.  Any four columns of H being independent for m >= 4, one corrupt shard i leaves
+ * suspect i and the n - 1 pairs that contain i, and two corrupt shards i, j -- at the same byte or at
+ * different ones -- leave no single suspect and the pair {i, j} alone.  A wave that keeps a single
+ * candidate evaluates no pair row.
+ * What the answer means: THREE corrupt shards can imitate a pair of other shards (3 + 2 >= m + 1
+ * for m = 4), and healing then rewrites good shards from bad ones; DESIGN.md section 4.8.1 has the
+ * measured rate.  Three or more corrupt shards are out of scope.
+ * ECX_E_ILLEGAL_ARGUMENT: m < 4 (two errors need 2 * 2 <= m), m > 8, n > 64 (a wave holds one 64-bit
+ * mask of single candidates), heal_id wanted with n + C(n,2) > 255 (n > 22), a negative count.  The
+ * pointers are checked after the counts (ECX_E_NULL).  nstripes == 0 touches nothing; byte_count == 0
+ * makes every stripe clean.  The first call of a codec on a device uploads its plans and must be
+ * made outside stream capture. */
+int ecx_rs_locate_corrupt2_batch(ecx_rs *rs, const uint8_t *base, int64_t stripe_stride, int64_t shard_stride,
+                                 int64_t nstripes, int64_t offset, int64_t byte_count, uint8_t *suspect,
+                                 int32_t *culprit, uint8_t *heal_id, void *stream);
+/* The same over the blocked layout, as ecx_rs_locate_corrupt_blocked_batch (and refusing what it
+ * refuses); heal_id feeds ecx_rs_decode_missing_blocked_batch_mixed. */
+int ecx_rs_locate_corrupt2_blocked_batch(ecx_rs *rs, const uint8_t *base, int64_t nstripes, int64_t byte_count,
+                                         int64_t block_bytes, uint8_t *suspect, int32_t *culprit, uint8_t *heal_id,
+                                         void *stream);
+
 /* The same two blocked batches (encodeParity / decodeMissing, ReedSolomon.java:94-108, :189-286)
  * from HOST memory, in place (base: nstripes * n * byte_count bytes of
  * pageable or pinned host memory in the blocked layout): the full blocks, then the tails, each a

@@ -155,6 +155,8 @@ RULES = {
     # the exports do
     "ecx_rs_locate_corrupt_batch": ((), [NN("nstripes", "offset", "byte_count")]),
     "ecx_rs_locate_corrupt_blocked_batch": ((), [NN("nstripes", "byte_count")]),
+    "ecx_rs_locate_corrupt2_batch": ((), [NN("nstripes", "offset", "byte_count")]),
+    "ecx_rs_locate_corrupt2_blocked_batch": ((), [NN("nstripes", "byte_count")]),
     "ecx_rs_blocked_layout": ((), [A("layout", "3")]),
     "ecx_rs_recommended_pitch": ((), [A("pitch", "1")]),
     "ecx_rs_decode_missing_blocked_batch": (("rs",), [A("shard_present", RS_N)]),

@@ -29,7 +29,7 @@ __all__ = [
     "lrc_encode", "lrc_encode_using_single", "lrc_decode", "sample_encode", "sample_decode",
     "device_count", "set_device", "fill_random", "count_mismatch", "shard_stripes",
     "ECChunk", "ECBlock", "ClayCodeHelper", "write_subchunk", "read_subchunk",
-    "PatternSet", "index_patterns", "ClayPatternSet", "index_erased",
+    "PatternSet", "index_patterns", "ClayPatternSet", "index_erased", "pair_index", "pair_of",
 ]
 
 
@@ -184,6 +184,25 @@ def _check_extent(buf, nbytes, what):
     avail = _avail_bytes(buf)
     if nbytes > 0 and avail is not None and nbytes > avail:
         raise EcxError(-5, f"{what}: the batch addresses {nbytes} bytes but the buffer holds {avail}")
+
+
+def pair_index(n: int, i: int, j: int) -> int:
+    """The place of the pair {i, j}, i < j, among the C(n,2) pairs of n shards in lexicographic
+    order: locateCorrupt2Batch's suspect n + pair_index(n, i, j) and doubleLossPatternSet()'s pattern."""
+    if not 0 <= i < j < n:
+        raise ValueError("pair_index needs 0 <= i < j < n")
+    return i * (2 * n - i - 1) // 2 + (j - i - 1)
+
+
+def pair_of(n: int, p: int):
+    """The pair (i, j) with pair_index(n, i, j) == p."""
+    if not 0 <= p < n * (n - 1) // 2:
+        raise ValueError("pair_of needs 0 <= p < C(n,2)")
+    i = 0
+    while p >= n - 1 - i:
+        p -= n - 1 - i
+        i += 1
+    return i, i + 1 + p
 
 
 def blocked_pack(shards, block_bytes: int, out=None):
@@ -855,6 +874,56 @@ class ReedSolomon:
         pattern of this set -- leaves a stripe untouched."""
         n = self.getTotalShardCount()
         return self.patternSet(1 - np.eye(n, dtype=np.uint8))
+
+    def _check_locate2_outputs(self, nstripes, suspect, culprit, healId):
+        n = self.getTotalShardCount()
+        width = n + n * (n - 1) // 2
+        _check_layout(suspect, width, 0, 0, nstripes, width, "suspect")
+        _check_layout(culprit, 8, 0, 0, nstripes, 8, "culprit")
+        if healId is not None:
+            _check_layout(healId, 1, 0, 0, nstripes, 1, "healId")
+
+    def locateCorrupt2Batch(self, shards, stripe_stride, shard_stride, nstripes, firstByte, byteCount, suspect,
+                            culprit, healId=None, stream=None) -> None:
+        """Which one or two shards of each stripe that fails isParityCorrect are corrupt, read-only
+        (ecx_rs_locate_corrupt2_batch; arguments of locateCorruptBatch).  ``suspect`` (device uint8
+        [nstripes][n + C(n,2)]) receives the n single suspects, then 1 at n + pair_index(n, i, j)
+        where replacing shards i and j together can make the stripe pass; ``culprit`` (device int32,
+        2 * nstripes) (-1, -1) for a clean stripe, (j, -1) for one corrupt shard, (i, j) for two,
+        (-2, -2) otherwise; ``healId`` (device uint8, nstripes, or None) j, n + pair_index(n, i, j)
+        or 255 -- the ids that decodeMissingBatchMixed takes with doubleLossPatternSet().  Codes
+        with 4 <= m <= 8 and n <= 64; heal ids for n <= 22."""
+        _check_layout(shards, stripe_stride, shard_stride, self.getTotalShardCount() - 1, nstripes,
+                      firstByte + byteCount, "shards")
+        self._check_locate2_outputs(nstripes, suspect, culprit, healId)
+        check(lib().ecx_rs_locate_corrupt2_batch(self._h, _dev_ptr(shards), stripe_stride, shard_stride, nstripes,
+                                                 firstByte, byteCount, _dev_ptr(suspect), _dev_ptr(culprit),
+                                                 None if healId is None else _dev_ptr(healId), _stream(stream)))
+
+    def locateCorrupt2BlockedBatch(self, base, nstripes, byteCount, suspect, culprit, healId=None, blockBytes=0,
+                                   stream=None) -> None:
+        """locateCorrupt2Batch over nstripes device-resident stripes in the blocked layout
+        (ecx_rs_locate_corrupt2_blocked_batch; arguments of locateCorruptBlockedBatch); ``healId``
+        feeds decodeMissingBlockedBatchMixed with doubleLossPatternSet()."""
+        _check_extent(base, nstripes * self.getTotalShardCount() * byteCount, "base")
+        self._check_locate2_outputs(nstripes, suspect, culprit, healId)
+        check(lib().ecx_rs_locate_corrupt2_blocked_batch(self._h, _dev_ptr(base), nstripes, byteCount, blockBytes,
+                                                         _dev_ptr(suspect), _dev_ptr(culprit),
+                                                         None if healId is None else _dev_ptr(healId),
+                                                         _stream(stream)))
+
+    def doubleLossPatternSet(self) -> "PatternSet":
+        """The n single-loss patterns in shard order (ids 0..n-1 mean what they mean in
+        singleLossPatternSet()), then the C(n,2) patterns "shards i and j missing" in pair order:
+        pattern n + pair_index(n, i, j) rebuilds both, so locateCorrupt2Batch's healId names the
+        pattern that heals each stripe.  n + C(n,2) <= 256 patterns: n <= 22."""
+        n = self.getTotalShardCount()
+        rows = [1 - np.eye(n, dtype=np.uint8)]
+        for p in range(n * (n - 1) // 2):
+            row = np.ones((1, n), np.uint8)
+            row[0, list(pair_of(n, p))] = 0
+            rows.append(row)
+        return self.patternSet(np.concatenate(rows))
 
     def decodeMissingBatch(self, shards, shardPresent, stripe_stride, shard_stride, nstripes, offset, byteCount,
                            stream=None):

@@ -117,6 +117,8 @@ SIGNATURES = {
     "ecx_rs_is_parity_correct_blocked_batch": (I, [P, P, I64, I64, I64, P, P]),
     "ecx_rs_locate_corrupt_batch": (I, [P, P, I64, I64, I64, I64, I64, P, P, P, P]),
     "ecx_rs_locate_corrupt_blocked_batch": (I, [P, P, I64, I64, I64, P, P, P, P]),
+    "ecx_rs_locate_corrupt2_batch": (I, [P, P, I64, I64, I64, I64, I64, P, P, P, P]),
+    "ecx_rs_locate_corrupt2_blocked_batch": (I, [P, P, I64, I64, I64, P, P, P, P]),
     "ecx_rs_is_parity_correct_blocked_batch_host": (I, [P, P, I64, I64, I64, P]),
     "ecx_rs_is_parity_correct_blocked_batch_host_devices": (I, [P, P, I64, I64, I64, P, P, I]),
     "ecx_rs_decode_missing_batch": (I, [P, P, P, I64, I64, I64, I64, I64, P]),

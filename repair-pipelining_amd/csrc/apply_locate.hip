@@ -17,6 +17,7 @@
 // culprit and heal id.  Every store is a plain vector store.
 #include "apply.hpp"
 #include "locate.hpp"
+#include "locate_launch.hpp"
 #include "layout_probe.hpp"  // note_device_launch
 
 #include <climits>
@@ -152,71 +153,22 @@ void launch_locate_k(dim3 grid, hipStream_t stream, const ApplyArgs &a, const Lo
     hipLaunchKernelGGL((k_gf_locate<SAFE, R>), grid, dim3(kBlockThreads), 0, stream, a, la);
 }
 
-// launch_check_core's skeleton (apply_check.hip) at ring depth 4: clears suspect[s / divisor][j]
-// when a test row of candidate j over bytes [0, nbytes) of stripe (unit) s is non-zero.
+// The passes of locate_launch.hpp with k_gf_locate: clears suspect[s / divisor][j] when a test row
+// of candidate j over bytes [0, nbytes) of stripe (unit) s is non-zero.
 void launch_locate_core(CompiledMap &cm, const LocateArgs &la, int n, const uint8_t *in, int64_t in_stripe_stride,
                         int64_t in_slot_stride, uint8_t *suspect, int64_t nstripes, int64_t nbytes, hipStream_t stream,
                         int64_t divisor = 1) {
-    const Tuning &tu = tuning();
-    const int rows = cm.max_tile_rows() <= 4 ? 4 : kTileRows;
-    const bool aligned = aligned16(in) && in_stripe_stride % 16 == 0 && in_slot_stride % 16 == 0;
-    const int64_t full = aligned ? nbytes / kChunkBytes : 0;
-    const int64_t tail = nbytes - full * kChunkBytes;
-    // the partial last chunk as a shifted full window (read-only: overlap is re-checked)
-    const bool fuse_tail = aligned && full >= 1 && tail > 0 && tail % 16 == 0;
-    const DevicePlan &plan = cm.plan_for_current_device(4);
-
-    ApplyArgs a{};
-    a.in = in;
-    a.out = suspect;
-    a.zero_page = zero_page_for_current_device();
-    a.in_stripe_stride = in_stripe_stride;
-    a.in_slot_stride = in_slot_stride;
-    a.out_stripe_stride = n;
-    a.out_slot_stride = 1;
-    a.nbytes = nbytes;
-    a.n_tiles = cm.n_tiles();
-    a.stagger = tu.stagger;
-    const bool misaligned128 = ((uintptr_t)in % 128) != 0 || in_stripe_stride % 128 != 0 || in_slot_stride % 128 != 0;
-    a.xcd_group = tu.xcd_group == 3 ? 3 : (tu.xcd_misaligned && misaligned128 ? 3 : 0);
-    a.xcd_run = tu.xcd_run;
-    a.tail_chunk = fuse_tail ? full : -1;
-    a.entries = plan.entries;
-    a.tiles = plan.tiles;
-    auto run = [&](bool safe, int64_t chunk_begin, int64_t n_chunks) {
-        if (n_chunks <= 0) return;
-        a.chunk_begin = chunk_begin;
-        a.n_chunks = n_chunks;
-        const int64_t per_stripe = n_chunks * a.n_tiles;
-        const int64_t stripes_per_launch = std::max<int64_t>(1, ((int64_t)1 << 30) / per_stripe);
-        for (int64_t s0 = 0; s0 < nstripes; s0 += stripes_per_launch) {
-            a.stripe_begin = s0;
-            const dim3 grid((unsigned)(std::min(stripes_per_launch, nstripes - s0) * per_stripe));
-            // blocked: the launch's suspect rows start at its first unit's stripe (launch_check_core)
-            const VerdictDiv vdiv = divisor > 1 ? verdict_div(divisor, s0) : VerdictDiv{};
-            const VerdictDiv *vd = divisor > 1 ? &vdiv : nullptr;
-            a.out = divisor > 1 ? suspect + (s0 / divisor) * n : suspect;
-            if (safe) {
-                if (rows == 4) launch_locate_k<true, 4>(grid, stream, a, la, vd);
-                else launch_locate_k<true, kTileRows>(grid, stream, a, la, vd);
-            } else {
-                if (rows == 4) launch_locate_k<false, 4>(grid, stream, a, la, vd);
-                else launch_locate_k<false, kTileRows>(grid, stream, a, la, vd);
-            }
-        }
-    };
-    const uint64_t notes0 = kernel_notes();
-    if (fuse_tail) {
-        run(false, 0, full + 1);
-    } else {
-        run(false, 0, full);
-        a.tail_chunk = -1;
-        run(true, full, (tail + kChunkBytes - 1) / kChunkBytes);  // (not noted: byte-safe)
-    }
-    if (kernel_notes() != notes0)
-        set_last_shape_order("stagger=" + std::to_string(a.stagger) + " xcd_group=" + std::to_string(a.xcd_group) +
-                             " xcd_run=" + std::to_string(a.xcd_group == 3 ? a.xcd_run : 0));
-    check_hip(hipGetLastError(), "k_gf_locate launch");
+    launch_locate_passes(cm, n, in, in_stripe_stride, in_slot_stride, suspect, nstripes, nbytes, divisor,
+                         "k_gf_locate launch",
+                         [&](bool safe, int rows, dim3 grid, const ApplyArgs &a, const VerdictDiv *vd) {
+                             if (safe) {
+                                 if (rows == 4) launch_locate_k<true, 4>(grid, stream, a, la, vd);
+                                 else launch_locate_k<true, kTileRows>(grid, stream, a, la, vd);
+                             } else {
+                                 if (rows == 4) launch_locate_k<false, 4>(grid, stream, a, la, vd);
+                                 else launch_locate_k<false, kTileRows>(grid, stream, a, la, vd);
+                             }
+                         });
 }
 
 // The device state of a locate, resident before anything is enqueued: a first use refused on a
@@ -231,13 +183,6 @@ LocateArgs resident(CompiledMap &cm, LocateSet &ls) {
     return LocateArgs{dp.entries, dp.tiles, lp.n_tiles};
 }
 
-void set_suspects(uint8_t *suspect, int64_t nstripes, int n, hipStream_t stream) {
-    const int64_t count = nstripes * n, blocks = (count + 255) / 256;
-    if (blocks > INT_MAX) throw Error(ECX_E_ILLEGAL_ARGUMENT, "too many stripes for one locate");
-    hipLaunchKernelGGL(k_set_suspects, dim3((unsigned)blocks), dim3(256), 0, stream, suspect, count);
-    check_hip(hipGetLastError(), "k_set_suspects launch");
-}
-
 void fold_suspects(const uint8_t *suspect, int n, int32_t *culprit, uint8_t *heal_id, int64_t nstripes,
                    hipStream_t stream) {
     hipLaunchKernelGGL(k_fold_suspects, dim3((unsigned)((nstripes + 255) / 256)), dim3(256), 0, stream, suspect, n,
@@ -245,6 +190,13 @@ void fold_suspects(const uint8_t *suspect, int n, int32_t *culprit, uint8_t *hea
     check_hip(hipGetLastError(), "k_fold_suspects launch");
 }
 }  // namespace
+
+void set_suspects(uint8_t *suspect, int64_t nstripes, int n, hipStream_t stream) {
+    const int64_t count = nstripes * n, blocks = (count + 255) / 256;
+    if (blocks > INT_MAX) throw Error(ECX_E_ILLEGAL_ARGUMENT, "too many stripes for one locate");
+    hipLaunchKernelGGL(k_set_suspects, dim3((unsigned)blocks), dim3(256), 0, stream, suspect, count);
+    check_hip(hipGetLastError(), "k_set_suspects launch");
+}
 
 // A start that is not 16-B aligned on 16-B strides is split as launch_check splits it: the bytes up
 // to the first 16-B boundary go to the byte-safe kernel, the rest to the vectorised one.

@@ -22,6 +22,7 @@
 #include "host_pipe.hpp"
 #include "layout_probe.hpp"  // note_device_launch
 #include "locate.hpp"
+#include "locate2.hpp"
 #include "pattern_set.hpp"
 #include "tune_table.hpp"
 #include "../../include/ecx_tune.h"
@@ -35,7 +36,7 @@ struct ecx_map {
 
 // What one of a codec's maps was built for.
 struct MapKey {
-    enum What { encode, check, decode, decode_partial, encode_partial, coding, helper_plane, locate };
+    enum What { encode, check, decode, decode_partial, encode_partial, coding, helper_plane, locate, locate2 };
     MapKey(What w, const std::vector<bool> &p = {}, int i = -1, int h = -1)
         : what(w), present(p.begin(), p.end()), index(i), helper(h) {}
     What what;
@@ -48,12 +49,14 @@ struct MapKey {
 };
 using MapMemo = Memo<MapKey, ecx_map>;  // plans live as long as the codec
 using LocateMemo = Memo<MapKey, LocateSet>;  // the locate plan (locate_plan.hpp), beside the check map
+using Locate2Memo = Memo<MapKey, Locate2Set>;  // the pair plan (locate2_plan.hpp), beside the locate plan
 
 struct ecx_rs {
     explicit ecx_rs(int k, int m) : code(k, m) {}
     RsCode code;
     MapMemo maps;
     LocateMemo locates;
+    Locate2Memo locates2;
 };
 
 // A pattern set (ecx.h): the decode maps of its patterns as one device plan.  `rs` is a reference
@@ -182,6 +185,31 @@ LocateSet *rs_locate_plan(ecx_rs *rs) {
     });
 }
 
+// The pair plan of a codec (4 <= m <= 8, n <= 64), built once beside its locate plan.
+Locate2Set *rs_locate2_plan(ecx_rs *rs) {
+    return rs->locates2.get({MapKey::locate2}, [&] {
+        const RsCode &c = rs->code;
+        std::vector<uint8_t> parity;
+        for (int p = 0; p < c.m(); ++p) parity.insert(parity.end(), c.parity_row(p), c.parity_row(p) + c.k());
+        Locate2Plan plan;
+        if (!build_locate2_plan(parity.data(), c.k(), c.m(), &plan))
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "no pair plan for this code");
+        return plan;
+    });
+}
+
+// What both locate2 entry points refuse about the codec and the outputs it was asked for.
+void check_locatable2(const ecx_rs *rs, const uint8_t *heal_id) {
+    const int m = rs->code.m(), n = rs->code.n();
+    if (m < kLocate2MinParity) throw Error(ECX_E_ILLEGAL_ARGUMENT, "locate2 needs m >= 4: two errors need 2 * 2 <= m");
+    if (m > kLocateMaxParity)
+        throw Error(ECX_E_ILLEGAL_ARGUMENT, "locate2 takes m <= " + std::to_string(kLocateMaxParity) + " (one check tile)");
+    if (n > kLocate2MaxShards)
+        throw Error(ECX_E_ILLEGAL_ARGUMENT, "locate2 takes n <= " + std::to_string(kLocate2MaxShards) + " (one 64-bit mask per wave)");
+    if (heal_id && n + n * (n - 1) / 2 > 255)
+        throw Error(ECX_E_ILLEGAL_ARGUMENT, "heal ids are bytes: n + C(n,2) must be <= 255 (n <= 22)");
+}
+
 // What both locate entry points refuse about the codec and the outputs it was asked for.
 void check_locatable(const ecx_rs *rs, const uint8_t *heal_id) {
     const int m = rs->code.m();
@@ -242,7 +270,7 @@ const char *ecx_status_string(int s) {
 }
 
 const char *ecx_last_error(void) { return g_last_error.c_str(); }
-int ecx_version(void) { return 108; }  // 1.08: 1.07 (1.06 + pattern sets) + the corrupt-shard locate
+int ecx_version(void) { return 109; }  // 1.09: 1.08 (1.07 + the corrupt-shard locate) + the two-shard locate
 
 // ---------------------------------------------------------------- device
 int ecx_device_count(int *count) {
@@ -775,6 +803,21 @@ int ecx_rs_locate_corrupt_batch(ecx_rs *rs, const uint8_t *base, int64_t stripe_
         if (!base || !suspect || !culprit) throw Error(ECX_E_NULL, "null device pointer");
         launch_locate(rs_check_plan(rs)->cm, *rs_locate_plan(rs), base + offset, stripe_stride, shard_stride, suspect,
                       culprit, heal_id, nstripes, byte_count, (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+
+int ecx_rs_locate_corrupt2_batch(ecx_rs *rs, const uint8_t *base, int64_t stripe_stride, int64_t shard_stride,
+                                 int64_t nstripes, int64_t offset, int64_t byte_count, uint8_t *suspect,
+                                 int32_t *culprit, uint8_t *heal_id, void *stream) {
+    return guarded(__func__, [&]() -> int {
+        if (!rs) throw Error(ECX_E_NULL, "null codec");
+        if (nstripes < 0 || offset < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        check_locatable2(rs, heal_id);
+        if (nstripes == 0) return ECX_OK;
+        if (!base || !suspect || !culprit) throw Error(ECX_E_NULL, "null device pointer");
+        launch_locate2(rs_check_plan(rs)->cm, *rs_locate_plan(rs), *rs_locate2_plan(rs), base + offset, stripe_stride,
+                       shard_stride, suspect, culprit, heal_id, nstripes, byte_count, (hipStream_t)stream);
         return ECX_OK;
     });
 }
@@ -1569,6 +1612,22 @@ int ecx_rs_locate_corrupt_blocked_batch(ecx_rs *rs, const uint8_t *base, int64_t
         if (!base || !suspect || !culprit) throw Error(ECX_E_NULL, "null device pointer");
         launch_locate_blocked(rs_check_plan(rs)->cm, *rs_locate_plan(rs), base, rs->code.n(), nstripes, byte_count,
                               block, suspect, culprit, heal_id, (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+
+int ecx_rs_locate_corrupt2_blocked_batch(ecx_rs *rs, const uint8_t *base, int64_t nstripes, int64_t byte_count,
+                                         int64_t block_bytes, uint8_t *suspect, int32_t *culprit, uint8_t *heal_id,
+                                         void *stream) {
+    return guarded(__func__, [&]() -> int {
+        if (!rs) throw Error(ECX_E_NULL, "null codec");
+        if (nstripes < 0 || byte_count < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        const int64_t block = resolve_block(rs->code.n(), byte_count, block_bytes);
+        check_locatable2(rs, heal_id);
+        if (nstripes == 0) return ECX_OK;
+        if (!base || !suspect || !culprit) throw Error(ECX_E_NULL, "null device pointer");
+        launch_locate2_blocked(rs_check_plan(rs)->cm, *rs_locate_plan(rs), *rs_locate2_plan(rs), base, rs->code.n(),
+                               nstripes, byte_count, block, suspect, culprit, heal_id, (hipStream_t)stream);
         return ECX_OK;
     });
 }

@@ -53,4 +53,8 @@ void launch_locate_blocked(CompiledMap &cm, LocateSet &ls, const uint8_t *base, 
                            int64_t byte_count, int64_t block, uint8_t *suspect, int32_t *culprit, uint8_t *heal_id,
                            hipStream_t stream);
 
+// suspect[i] = 1 for all nstripes * n bytes (k_set_suspects): what every locate starts with, n being
+// the bytes of a stripe's suspect row.
+void set_suspects(uint8_t *suspect, int64_t nstripes, int n, hipStream_t stream);
+
 }  // namespace ecx

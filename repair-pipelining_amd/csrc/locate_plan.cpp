@@ -30,6 +30,36 @@ void split_tables(uint8_t c, uint32_t *out) {
 }
 }  // namespace
 
+void locate_set_coefficient(uint32_t *rec, int r, uint8_t c) {
+    if (c == 1) rec[2] |= 1u << r;
+    else if (c) {
+        rec[1] |= 1u << r;
+        split_tables(c, rec + 4 + 5 * r);
+    }
+}
+
+uint8_t locate_row_or(const uint32_t *ent, int m, uint32_t r, const uint8_t *syn, int64_t syn_stride, int64_t b0,
+                      int64_t b1) {
+    auto table_byte = [](uint32_t lo, uint32_t hi, int idx) {
+        return (uint8_t)((idx < 4 ? lo : hi) >> (8 * (idx & 3)));
+    };
+    uint8_t nz = 0;
+    for (int64_t b = b0; b < b1; ++b) {
+        uint8_t v = 0;
+        for (int q = 0; q < m; ++q) {
+            const uint32_t *rec = ent + (size_t)q * kLocateEntryDwords;
+            const uint32_t *tb = rec + 4 + 5 * r;
+            const uint8_t x = syn[q * syn_stride + b];
+            if (rec[2] & (1u << r)) v ^= x;
+            if (rec[1] & (1u << r))
+                v ^= table_byte(tb[0], tb[1], x & 7) ^ table_byte(tb[2], tb[3], (x >> 3) & 7) ^
+                     table_byte(tb[4], tb[4], x >> 6);
+        }
+        nz |= v;
+    }
+    return nz;
+}
+
 bool build_locate_plan(const uint8_t *parity, int k, int m, LocatePlan *out) {
     if (!parity || !out || k < 1 || m < 2 || m > kLocateMaxParity || k + m > 256) return false;
     for (int j = 0; j < k; ++j)
@@ -46,12 +76,7 @@ bool build_locate_plan(const uint8_t *parity, int k, int m, LocatePlan *out) {
     // coefficient c of syndrome p in test row `row`
     auto put = [&](int row, int p, uint8_t c) {
         const int t = row / kLocateTileRows, r = row % kLocateTileRows;
-        uint32_t *rec = pl.entries.data() + ((size_t)t * m + p) * kLocateEntryDwords;
-        if (c == 1) rec[2] |= 1u << r;
-        else if (c) {
-            rec[1] |= 1u << r;
-            split_tables(c, rec + 4 + 5 * r);
-        }
+        locate_set_coefficient(pl.entries.data() + ((size_t)t * m + p) * kLocateEntryDwords, r, c);
     };
     for (int j = 0; j < n; ++j) {
         for (int i = 0; i < m - 1; ++i) {
@@ -81,9 +106,6 @@ bool build_locate_plan(const uint8_t *parity, int k, int m, LocatePlan *out) {
 }
 
 bool emulate_locate(const LocatePlan &p, const uint8_t *syn, int64_t syn_stride, int64_t len, uint8_t *suspect) {
-    auto table_byte = [](uint32_t lo, uint32_t hi, int idx) {
-        return (uint8_t)((idx < 4 ? lo : hi) >> (8 * (idx & 3)));
-    };
     if (p.k < 1 || p.m < 2 || p.m > kLocateMaxParity || p.k + p.m > 256) return false;
     const int n = p.k + p.m, rows = n * (p.m - 1);
     if (p.n_tiles != (rows + kLocateTileRows - 1) / kLocateTileRows) return false;
@@ -103,21 +125,7 @@ bool emulate_locate(const LocatePlan &p, const uint8_t *syn, int64_t syn_stride,
         for (uint32_t r = 0; r < nr; ++r) {
             const uint32_t cand = tile[4 + r];
             if (cand >= (uint32_t)n || (int)cand != p.candidate[(size_t)t * kLocateTileRows + r]) return false;
-            uint8_t nz = 0;
-            for (int64_t b = 0; b < len; ++b) {
-                uint8_t v = 0;
-                for (int q = 0; q < p.m; ++q) {
-                    const uint32_t *rec = ent + (size_t)q * kLocateEntryDwords;
-                    const uint32_t *tb = rec + 4 + 5 * r;
-                    const uint8_t x = syn[q * syn_stride + b];
-                    if (rec[2] & (1u << r)) v ^= x;
-                    if (rec[1] & (1u << r))
-                        v ^= table_byte(tb[0], tb[1], x & 7) ^ table_byte(tb[2], tb[3], (x >> 3) & 7) ^
-                             table_byte(tb[4], tb[4], x >> 6);
-                }
-                nz |= v;
-            }
-            if (nz) suspect[cand] = 0;
+            if (locate_row_or(ent, p.m, r, syn, syn_stride, 0, len)) suspect[cand] = 0;
         }
     }
     return true;

@@ -54,4 +54,11 @@ bool build_locate_plan(const uint8_t *parity, int k, int m, LocatePlan *out);
 // outside 1..kLocateTileRows, mask bits at or above the row count, a candidate outside 0..n-1).
 bool emulate_locate(const LocatePlan &p, const uint8_t *syn, int64_t syn_stride, int64_t len, uint8_t *suspect);
 
+// What both this plan and the pair plan (locate2_plan.hpp) are written and read with: coefficient c
+// of a record's syndrome in test row r of its tile (mask bit, and the split tables of a general c);
+// and the OR over bytes [b0, b1) of row r of the tile whose m records start at `ent`.
+void locate_set_coefficient(uint32_t *rec, int r, uint8_t c);
+uint8_t locate_row_or(const uint32_t *ent, int m, uint32_t r, const uint8_t *syn, int64_t syn_stride, int64_t b0,
+                      int64_t b1);
+
 }  // namespace ecx
