@@ -467,6 +467,40 @@ int ecx_clay_map(ecx_clay *clay, const ecx_map **out);
 int ecx_clay_perform_coding_batch(ecx_clay *clay, const uint8_t *in, int64_t in_stripe_stride,
                                   int64_t in_sub_stride, uint8_t *out, int64_t out_stripe_stride,
                                   int64_t out_sub_stride, int64_t nstripes, int64_t buf_size, void *stream);
+/* isParityCorrect for Clay stripes: whether each of nstripes device-resident stripes of the
+ * geometry ecx_clay_create_shortened(data_units, parity_units, virtual_units, ...) is still a
+ * codeword, in one read-only launch (k_clay_check; geometries of at most 16 syndrome rows, Clay(2,2)
+ * and Clay(4,2), run their dense syndrome map on k_gf_check instead, which measured faster there).
+ * The layout is ecx_clay_perform_coding_batch's input layout: real slot z*n + node (n = data_units + parity_units real nodes, virtual nodes hold
+ * no slot) of stripe s lies at base + s*stripe_stride + slot*sub_stride and is buf_size bytes long.
+ * verdict is a device byte array of nstripes.
+ * verdict[s] == 1 means: over bytes [0, buf_size) of every sub-chunk, the parity nodes of stripe s
+ * are exactly what encoding its data nodes gives -- the stripe is a codeword.  It is a codeword
+ * test and nothing more: a 0 does not say which node is corrupt, nor how many are, and a 1 says
+ * nothing about bytes past buf_size (the padding of a layout with sub_stride > buf_size).
+ * The call only enqueues on `stream` and writes nothing but verdict.
+ * Checked in this order: negative counts ECX_E_ILLEGAL_ARGUMENT; nstripes == 0 returns ECX_OK with
+ * nothing touched; null base or verdict ECX_E_NULL; a negative stride, or an extent beyond int64_t,
+ * ECX_E_ILLEGAL_ARGUMENT.  buf_size == 0 makes every stripe pass.
+ * Geometries: every one ecx_clay_create_shortened accepts whose nodes fill the q x t grid, with
+ * parity_units <= 8 (one accumulator tile), and whose check program the planner can prove (every
+ * encoded stripe has zero syndromes, and only those); any other is refused with
+ * ECX_E_ILLEGAL_ARGUMENT and the reason in ecx_last_error.  The proof runs on the geometry's first
+ * call in the process (about 0.1 s for Clay(12,4)) and is kept with the shared codec.
+ * The first call for a geometry on a device uploads its node records and must be made outside
+ * stream capture (under capture it returns ECX_E_DEVICE and leaves no node behind); later calls
+ * may be captured and replayed.
+ * Lifetime: the proved program and its device records belong to the shared codec of the geometry,
+ * the object ecx_clay_create_shortened(data_units, parity_units, virtual_units, NULL, 0, &h)
+ * returns.  The call itself holds that codec only while it runs; afterwards the codec is idle and
+ * may be evicted (its device records freed) once 64 other codecs have been released.  A caller who
+ * checks repeatedly should hold such a handle between calls, so the proof and the upload are paid
+ * once; a caller who CAPTURES the call MUST hold one from before the warm-up call until the graph
+ * is destroyed, because the graph's kernel nodes keep pointers to those records, and must not
+ * destroy it while enqueued work is in flight.  The Python and Java wrappers hold it for you. */
+int ecx_clay_is_parity_correct_batch(int data_units, int parity_units, int virtual_units, const uint8_t *base,
+                                     int64_t stripe_stride, int64_t sub_stride, int64_t nstripes, int64_t buf_size,
+                                     uint8_t *verdict, void *stream);
 
 /* A Clay pattern set -- performCoding (ClayCodeErasureDecodingStep.java:53-107) over a batch whose
  * stripes lost DIFFERENT nodes, in one launch.  The set holds up to 256 erased-node lists of one

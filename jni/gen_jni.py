@@ -175,6 +175,9 @@ RULES = {
                                          A("erased", "int_array_sum(env, n_erased, npatterns)")]),
     "ecx_clay_pattern_set_info": ((), [A("npatterns", "1"), A("nodes", "1"), A("alpha", "1"), A("max_erased", "1")]),
     "ecx_clay_perform_coding_batch_mixed": ((), [NN("nstripes", "buf_size")]),
+    # the Clay codeword check takes a geometry and device addresses only; its counts are refused
+    # here as the export does
+    "ecx_clay_is_parity_correct_batch": ((), [NN("nstripes", "buf_size")]),
     # the hop with a list and a node per stripe: addresses only, as the other mixed device calls
     "ecx_clay_partial_batch_mixed": ((), [NN("nstripes", "buf_size")]),
     "ecx_clay_perform_coding_mixed_batch_host": ((), [NN("nstripes", "buf_size")]),

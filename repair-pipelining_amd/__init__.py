@@ -1269,6 +1269,56 @@ class ClayCodeErasureDecodingStep:
                                                                len(devs)))
 
 
+class ClayParityCheck:
+    """isParityCorrect for Clay stripes (ecx_clay_is_parity_correct_batch): whether each stripe of a
+    device-resident batch is still a codeword of Clay(dataUnits, parityUnits) -- shortened by
+    ``virtualUnits`` zero data nodes -- in one read-only launch.  A codeword test: a failing stripe's
+    verdict does not say which node is corrupt."""
+
+    def __init__(self, dataUnits: int, parityUnits: int, virtualUnits: int = 0):
+        self.dataUnits, self.parityUnits, self.virtualUnits = int(dataUnits), int(parityUnits), int(virtualUnits)
+        # The handle is kept until close() / __del__: it holds the shared codec, and with it the proved
+        # check program and its device records, which the kernel nodes of a captured call point to.
+        self._h = None
+        h = ctypes.c_void_p()
+        check(lib().ecx_clay_create_shortened(self.dataUnits, self.parityUnits, self.virtualUnits, None, 0,
+                                              ctypes.byref(h)))
+        self._h = h
+        q, t, a = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        check(lib().ecx_clay_geometry(h, ctypes.byref(q), ctypes.byref(t), ctypes.byref(a)))
+        self._geometry = (q.value, t.value, a.value, self.dataUnits + self.parityUnits)
+
+    def close(self) -> None:
+        """Release the codec reference; idempotent.  Not while enqueued work is in flight, and not
+        before a graph that captured isParityCorrectBatch is destroyed."""
+        if getattr(self, "_h", None):
+            h, self._h = self._h, None
+            lib().ecx_clay_destroy(h)
+
+    def __del__(self):
+        self.close()
+
+    def geometry(self):
+        """(q, t, alpha, n_real): a stripe holds alpha * n_real sub-chunks, real slot z * n_real + node."""
+        return self._geometry
+
+    def isParityCorrectBatch(self, stripes, stripe_stride, sub_stride, nstripes, bufSize, verdict, stream=None) -> None:
+        """Over nstripes device-resident stripes in performCodingBatch's input layout (real slot
+        z * n_real + node of stripe s at s * stripe_stride + slot * sub_stride, bufSize bytes each):
+        the device uint8 array ``verdict`` (nstripes bytes) receives 1 for each stripe that is a
+        codeword over [0, bufSize) of every sub-chunk, else 0.  Enqueued on ``stream``; read verdict
+        after synchronising.  The first call of a geometry on a device must be outside stream capture;
+        keep this object alive as long as a graph that captured the call."""
+        if not self._h:
+            raise EcxError(-1, "ClayParityCheck is closed")
+        _, _, alpha, n_real = self._geometry
+        _check_layout(stripes, stripe_stride, sub_stride, alpha * n_real - 1, nstripes, bufSize, "stripes")
+        _check_layout(verdict, 1, 0, 0, nstripes, 1, "verdict")
+        check(lib().ecx_clay_is_parity_correct_batch(self.dataUnits, self.parityUnits, self.virtualUnits,
+                                                     _dev_ptr(stripes), stripe_stride, sub_stride, nstripes, bufSize,
+                                                     _dev_ptr(verdict), _stream(stream)))
+
+
 class ClayPatternSet:
     """ecx_clay_pattern_set: up to 256 erased-node lists of one Clay geometry as one device plan,
     for performCoding (ClayCodeErasureDecodingStep.java:53-107) over a batch whose stripes lost

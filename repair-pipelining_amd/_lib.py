@@ -144,6 +144,7 @@ SIGNATURES = {
     "ecx_clay_decode_single_helper": (I, [P, PP, I, PP, I, I]),
     "ecx_clay_map": (I, [P, ctypes.POINTER(P)]),
     "ecx_clay_perform_coding_batch": (I, [P, P, I64, I64, P, I64, I64, I64, I64, P]),
+    "ecx_clay_is_parity_correct_batch": (I, [I, I, I, P, I64, I64, I64, I64, P, P]),
     "ecx_clay_pattern_set_create": (I, [I, I, I, P, P, I, ctypes.POINTER(P)]),
     "ecx_clay_pattern_set_destroy": (None, [P]),
     "ecx_clay_pattern_set_info": (I, [P, PI, PI, PI, PI]),

@@ -15,6 +15,7 @@
 #include "api_maps.hpp"
 #include "blocked_layout.hpp"
 #include "check_blocked.hpp"
+#include "clay_check.hpp"
 #include "clay_rtc.hpp"
 #include "codec_cache.hpp"
 #include "map_rtc.hpp"
@@ -76,6 +77,10 @@ struct ecx_clay {
     std::unique_ptr<ClayRtc> rtc;
     int rtc_state = 0;  // 0 = not tried, 1 = available, -1 = not representable
     std::string rtc_why;
+    // The geometry's codeword test (ecx_clay_is_parity_correct_batch) and its device records, proved on first use.
+    std::unique_ptr<ClayCheck> check;
+    int check_state = 0;  // 0 = not tried, 1 = proved, -1 = refused
+    std::string check_why;
 };
 
 namespace {
@@ -270,7 +275,7 @@ const char *ecx_status_string(int s) {
 }
 
 const char *ecx_last_error(void) { return g_last_error.c_str(); }
-int ecx_version(void) { return 109; }  // 1.09: 1.08 (1.07 + the corrupt-shard locate) + the two-shard locate
+int ecx_version(void) { return 110; }  // 1.10: 1.09 (1.08 + the two-shard locate) + the Clay codeword check
 
 // ---------------------------------------------------------------- device
 int ecx_device_count(int *count) {
@@ -1146,6 +1151,87 @@ int ecx_clay_perform_coding_batch(ecx_clay *clay, const uint8_t *in, int64_t in_
         return ECX_OK;
     });
 }
+
+namespace {
+// The codeword test of a geometry, on the registry's codec without erasures: the planner's proof
+// runs once, and a refusal is kept with its reason.
+ClayCheck *clay_check(ecx_clay *clay) {
+    std::lock_guard<std::mutex> lk(clay->mu);
+    if (clay->check_state == 0) {
+        try {
+            clay->check.reset(new ClayCheck(clay_check_program(clay->pl)));
+            clay->check_state = 1;
+        } catch (const Error &e) {
+            clay->check_state = -1;
+            clay->check_why = e.what();
+        }
+    }
+    if (clay->check_state != 1) throw Error(ECX_E_ILLEGAL_ARGUMENT, "no Clay parity check for this geometry: " + clay->check_why);
+    return clay->check.get();
+}
+
+// The program's dense syndrome map as an ordinary check map (rows z * m + p over the real slots).
+constexpr int kClayCheckDenseRows = 16;
+ecx_map *clay_check_dense_map(ecx_clay *clay, ClayCheck *cc) {
+    return clay->maps.get({MapKey::check}, [&] { return cc->program().compose(); });
+}
+
+// A reference on the registry's codec of a geometry for the length of one call.
+struct ClayRef {
+    ClayRef(int k, int m, int v)
+        : clay(clay_registry().get(std::make_tuple(k, m, v, std::vector<int>{}, 0), [&] { return new ecx_clay(k, m, {}, v); })) {}
+    ~ClayRef() { clay_registry().release(clay); }
+    ClayRef(const ClayRef &) = delete;
+    ClayRef &operator=(const ClayRef &) = delete;
+    ecx_clay *clay;
+};
+}  // namespace
+
+int ecx_clay_is_parity_correct_batch(int data_units, int parity_units, int virtual_units, const uint8_t *base,
+                                     int64_t stripe_stride, int64_t sub_stride, int64_t nstripes, int64_t buf_size,
+                                     uint8_t *verdict, void *stream) {
+    return guarded(__func__, [&]() -> int {
+        if (data_units < 1 || parity_units < 1 || virtual_units < 0 || nstripes < 0 || buf_size < 0)
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative count");
+        if (nstripes == 0) return ECX_OK;
+        if (!base || !verdict) throw Error(ECX_E_NULL, "null device pointer");
+        if (stripe_stride < 0 || sub_stride < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative stride");
+        const ClayRef ref(data_units, parity_units, virtual_units);  // (refuses what ecx_clay_create_shortened does)
+        const ClayPlanner &pl = ref.clay->pl;
+        if (!extent_fits({{nstripes, stripe_stride}, {(int64_t)pl.n_real() * pl.alpha(), sub_stride}}, buf_size))
+            throw Error(ECX_E_ILLEGAL_ARGUMENT, "negative stride, or the batch's extent is beyond int64_t");
+        ClayCheck *cc = clay_check(ref.clay);
+        // Geometries whose dense syndrome map has at most 16 rows (Clay(2,2), Clay(4,2)) run it as an
+        // ordinary check map on k_gf_check: measured faster there than one workgroup per plane (0.85 of
+        // its time on Clay(4,2)), and the simpler path.
+        if (pl.m() * pl.alpha() <= kClayCheckDenseRows)
+            launch_check(clay_check_dense_map(ref.clay, cc)->cm, base, stripe_stride, sub_stride, verdict, nstripes,
+                         buf_size, (hipStream_t)stream);
+        else
+            launch_clay_check(*cc, base, stripe_stride, sub_stride, verdict, nstripes, buf_size, (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+
+#if ECX_DIAG
+// DIAG only (scripts/clay_check_ab.py): either route forced for any geometry -- dense 1: the
+// existing k_gf_check over the program's dense syndrome map, 0: k_clay_check.
+extern "C" int ecx_diag_clay_check_route_batch(int dense, int data_units, int parity_units, int virtual_units,
+                                               const uint8_t *base, int64_t stripe_stride, int64_t sub_stride,
+                                               int64_t nstripes, int64_t buf_size, uint8_t *verdict, void *stream) {
+    return guarded(__func__, [&]() -> int {
+        if (!base || !verdict || nstripes <= 0 || buf_size < 0) throw Error(ECX_E_ILLEGAL_ARGUMENT, "arguments");
+        const ClayRef ref(data_units, parity_units, virtual_units);
+        ClayCheck *cc = clay_check(ref.clay);
+        if (dense)
+            launch_check(clay_check_dense_map(ref.clay, cc)->cm, base, stripe_stride, sub_stride, verdict, nstripes,
+                         buf_size, (hipStream_t)stream);
+        else
+            launch_clay_check(*cc, base, stripe_stride, sub_stride, verdict, nstripes, buf_size, (hipStream_t)stream);
+        return ECX_OK;
+    });
+}
+#endif
 
 // ---------------------------------------------------------------- Clay pattern sets
 // A Clay pattern set (ecx.h): the standard-null-pattern performCoding maps of its erased-node
